@@ -32,13 +32,16 @@ one host thread and stream per device, ncclCommInitAll over devices
 0..N-1 -- WarpDB::query_multi_gpu_sum / _group / _topk), for sum, group and
 topk; its per-step time includes the collective and the host read-back.
 
-Beside the headline (`secondary`, each line timed the same way and checked
-after timing; `exchange_ms` = HIP events around the collective + device merge
-on multi-rank runs, read from up to 50 steps after the timed ones;
-`host_issue_ms` = the host's time to issue one step): SUM and GROUP BY on the
-same shards, C2 at its own 1e8
-rows per GPU, C5 (ORDER BY price DESC LIMIT 5 + discount()), and the
-strong-scaled C3 (1e9 rows) and C4 (8e9 rows) lines over all GPUs.
+A plain run sets up, warms up, times the K steps and prints the line;
+--dump-outputs DIR also writes what the last timed step computed, as
+DIR/<name>.npy.  Everything else is behind --full: the result check after
+timing, the CPU baseline, `exchange_ms` (HIP events around the collective +
+device merge on multi-rank runs, read from up to 50 steps after the timed
+ones) and the lines beside the headline (`secondary`, each timed the same
+way and checked after timing; `host_issue_ms` = the host's time to issue
+one step): SUM and GROUP BY on the same shards, C2 at its own 1e8 rows per
+GPU, C5 (ORDER BY price DESC LIMIT 5 + discount()), and the strong-scaled
+C3 (1e9 rows) and C4 (8e9 rows) lines over all GPUs.
 
 Prints ONE JSON line (rank 0).
 """
@@ -118,7 +121,16 @@ def parse():
                    help="project only: skip the C5 line (ORDER BY price DESC LIMIT 5 + discount())")
     p.add_argument("--keys", type=int, default=1024,
                    help="group: distinct int32 keys, uniform over [0, keys) (BASELINE C3: 1K)")
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="beside the headline: the post-timing result check, the secondary lines, the exchange "
+                        "timing and the CPU baseline (each still switched off by its own --no-* option)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step computed as DIR/<name>.npy (float32 / float64; a fixed "
+                        "seeded sample of a large array)")
+    args = p.parse_args()
+    if not args.full:  # a plain run: set-up, warm-up, the timed steps, the result line
+        args.no_cpu_baseline = args.no_check = args.no_secondary = True
+    return args
 
 
 # ------------------------------------------------------------ CPU baseline
@@ -267,6 +279,36 @@ def roofline(bytes_per_launch, kern_ms, read_bytes, kname, traffic, timing):
             "kernel_ms": round(kern_ms, 4), "bytes_per_launch": int(bytes_per_launch), "timing": timing,
             # BASELINE.md's "HBM-read roofline": input bytes only over the same time
             "read_only_frac": round(read_bytes / (kern_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
+
+
+# ------------------------------------------------- --dump-outputs
+DUMP_SAMPLE = 2_000_000  # elements kept of a larger array: three such float64 arrays stay under 64 MB
+
+
+def dump_outputs(dirname, arrays, world=1, rank=0):
+    """Write each array (a torch tensor or anything numpy converts) as
+    DIR/<name>.npy (rank 0; DIR/<name>_rank<r>.npy on the other ranks):
+    float32 stays float32, everything else becomes float64 (exact for the
+    int32 / int64 row ids and counts here).  An array of more than
+    DUMP_SAMPLE / world elements is sampled at sorted positions drawn from a
+    generator seeded with 0, so the positions depend only on its length:
+    arrays of one length (values and their row ids) are sampled at the same
+    positions, and so are two builds that computed the same number of rows."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dirname, exist_ok=True)
+    cap = max(1, DUMP_SAMPLE // max(1, world))
+    for name, a in arrays.items():
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.atleast_1d(np.asarray(a)))
+        t = t.detach().reshape(-1)
+        if t.numel() > cap:
+            g = torch.Generator().manual_seed(0)
+            pos = torch.randint(0, t.numel(), (cap,), generator=g).sort().values
+            t = t[pos.to(t.device)]
+        t = t.cpu()
+        t = t if t.dtype == torch.float32 else t.double()
+        np.save(os.path.join(dirname, name + (".npy" if rank == 0 else f"_rank{rank}.npy")), t.numpy())
 
 
 # PMC traffic profiles (profiles/pmc_<workload>.json, written by
@@ -502,11 +544,18 @@ def main_ranks(args):
 
         def step():
             sq.compact_device(expr, aux, out_v, out_i, 4, counts)
+
+        def outputs(last):  # the passing rows' values and shard-local row ids, in row order
+            c = int(counts.item())
+            return {"values": out_v[:c], "row_index": out_i[:c], "count": counts}
     elif workload == "dense":
         out_v = torch.empty(max(1, n), dtype=torch.float32, device="cuda")
 
         def step():
             wx.project_filter(sq.table, expr, aux, sq.launch, wx.MODE_DENSE_FILL, out_v.data_ptr(), 0, 4, 0)
+
+        def outputs(last):
+            return {"values": out_v[:n]}
     elif workload == "sort":
         out_v = torch.empty(max(1, n), dtype=torch.float32, device="cuda")
 
@@ -523,22 +572,37 @@ def main_ranks(args):
             wx.project_filter(sq.table, expr, None, sq.launch_aux, wx.MODE_COMPACT, out_v.data_ptr(), 0, 4, 0,
                               d_count=counts.data_ptr())
             wx.sort_float(out_v.data_ptr(), n, True, sq.launch)  # synchronous, as jit_sort_float
+
+        def outputs(last):
+            return {"sorted": out_v[:n]}
     elif workload == "sum":
         res = torch.zeros(2, dtype=torch.float64, device="cuda")
 
         def step():
             sq.sum_device(expr, aux, res)
+
+        def outputs(last):
+            return {"sum_count": res}
     elif workload == "group":
         def step():
             if coll and args.keys > wx.GROUP_WINDOW_BINS:
                 # many keys: every shard's groups as one list record, ONE
                 # all-gather, wx_group_merge_lists on the device
-                sq.group_sum_lists_device(expr, aux, None, group_capacity(args.keys))
-            else:
-                sq.group_sum_device(expr, aux, None, 0, group_capacity(args.keys))
+                return sq.group_sum_lists_device(expr, aux, None, group_capacity(args.keys))
+            return sq.group_sum_device(expr, aux, None, 0, group_capacity(args.keys))
+
+        def outputs(last):  # the groups in ascending key order (none when the step flagged an overflow)
+            gk, gs, gc, ng = last
+            m = max(0, min(gk.numel(), int(ng.item())))
+            return {"keys": gk[:m], "sums": gs[:m], "counts": gc[:m], "n_groups": ng}
     else:
         def step():  # results stay in HBM like the other workloads' (no host round trip per query)
-            sq.topk_merged_device(expr, None, aux, 5, True)
+            return sq.topk_merged_device(expr, None, aux, 5, True)
+
+        def outputs(last):
+            tk, ti, tv, tn = last
+            m = max(0, min(tk.numel(), int(tn.item())))
+            return {"keys": tk[:m], "rows": ti[:m], "values": tv[:m], "count": tn}
 
     verbose = os.environ.get("WARPDB_BENCH_VERBOSE")
 
@@ -546,7 +610,7 @@ def main_ranks(args):
         if verbose:
             print(f"[bench rank {rank}] {what} {time.strftime('%H:%M:%S')}", file=sys.stderr, flush=True)
 
-    def timed(step_fn, warm_s=0.0, sq_ex=None):
+    def timed(step_fn, warm_s=0.0, sq_ex=None, after=None):
         """W warm-up steps (secondary lines: and at least warm_s seconds of
         them), then exactly K steps between barrier + synchronize;
         (elapsed s, average timed-kernel ms, launches, exchange ms, host
@@ -555,7 +619,8 @@ def main_ranks(args):
         exchange (collective + device merge): its average is the fourth value
         (None on one rank).  Those events stay out of the timed steps: an
         event record with the default system-scope fence costs several us
-        of stream time, ~10 % of a 1.25e8-row GROUP BY step."""
+        of stream time, ~10 % of a 1.25e8-row GROUP BY step.  `after` is
+        called with what the last timed step returned, before those steps."""
         for _ in range(args.warmup):
             step_fn()
         if warm_s > 0:
@@ -581,8 +646,9 @@ def main_ranks(args):
             dist.barrier()
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        last = None
         for _ in range(args.steps):
-            step_fn()
+            last = step_fn()
         issued = time.perf_counter() - t0  # the host's time to issue the K steps
         torch.cuda.synchronize()
         if coll:
@@ -591,6 +657,8 @@ def main_ranks(args):
         k_ms, nl = wx.timing_read()
         wx.check(L)
         k_avg = k_ms / max(1, nl)
+        if after is not None:
+            after(last)
         ex_ms = None
         if sq_ex is not None and coll:  # exchange time: more steps after the timed region (same count on every rank)
             sq_ex.time_exchanges(min(50, args.steps))
@@ -608,7 +676,13 @@ def main_ranks(args):
         return el, k_avg, nl, ex_ms, round(issued / max(1, args.steps) * 1e3, 4)
 
     mark("warm-up")
-    elapsed, kern_avg_ms, launches, ex_main, issue_main = timed(step, sq_ex=sq)
+
+    def dump(last):  # right after the timed steps: every later step writes the same buffers
+        mark("dump outputs")
+        dump_outputs(args.dump_outputs, outputs(last), world, rank)
+
+    elapsed, kern_avg_ms, launches, ex_main, issue_main = timed(step, sq_ex=sq if args.full else None,
+                                                                after=dump if args.dump_outputs else None)
 
     # algorithmic bytes per launch of the dominant kernel
     passing = int(counts.item()) if workload == "project" else None
@@ -836,18 +910,24 @@ def main_api(args):
     shards.take_timing()  # discard the warm-up's (nothing is timed yet)
     shards.set_timing(True, False)  # HIP events around each shard's main kernel (no system fence)
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = step()
     elapsed = time.perf_counter() - t0
     shards.set_timing(False, False)
     kt = shards.take_timing()
-    # the exchange (collective + merge, an event pair per device) from more
-    # steps after the timed region, as the torchrun line reads exchange_ms
-    shards.set_timing(False, True)
-    for _ in range(min(50, args.steps)):
-        step()
-    shards.set_timing(False, False)
-    ex_ms = shards.take_timing()["exchange_ms"]
+    if args.dump_outputs:  # the host values the last timed call returned
+        names = {"sum": ("sum", "count"), "group": ("keys", "sums", "counts"), "topk": ("keys", "rows", "values")}
+        dump_outputs(args.dump_outputs, dict(zip(names[workload], last)))
+    ex_ms = None
+    if args.full:
+        # the exchange (collective + merge, an event pair per device) from more
+        # steps after the timed region, as the torchrun line reads exchange_ms
+        shards.set_timing(False, True)
+        for _ in range(min(50, args.steps)):
+            step()
+        shards.set_timing(False, False)
+        ex_ms = shards.take_timing()["exchange_ms"]
     n_max = max(e - b for _, b, e in shards.ranges())
     line = line_common(args, shards.num_shards, n_total, elapsed, workload)
     line["config"] = {"workload": f"{query} ({workload})", "rows_per_gpu": n_max, "total_rows": n_total,
@@ -868,7 +948,7 @@ def main_api(args):
                                 if kt["launches"] else "whole step (no kernel events were read)")
     line["kernel_launches"] = kt["launches"]
     line["exchange_ms"] = None if ex_ms is None else round(ex_ms, 4)
-    line["check"] = api_check(workload, step(), n_total, shards)
+    line["check"] = api_check(workload, step(), n_total, shards) if args.full else None
     line["cpu_baseline"] = cpu_leg(args, workload) if shards.num_shards == 1 else None
     print(json.dumps(line), flush=True)
 

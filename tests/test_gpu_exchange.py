@@ -386,7 +386,7 @@ def _bench_ranks(n, workload, extra, env_extra=None):
     env.update(env_extra or {})
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", str(n), "--workload", workload, "--steps", "3", "--warmup", "1",
+                        "--gpus", str(n), "--workload", workload, "--steps", "3", "--warmup", "1", "--full",
                         "--no-cpu-baseline", *extra],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
@@ -435,7 +435,7 @@ def test_bench_api_rccl_one_device(workload):
     ncclCommInitAll communicator: ncclAllReduce / ncclAllGather run."""
     env = dict(os.environ, WARPDB_EXCHANGE_ONE_RANK="1")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--api", "--gpus", "1", "--workload", workload,
-                        "--rows", "1e7", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
+                        "--rows", "1e7", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=300)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     d = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")][-1]

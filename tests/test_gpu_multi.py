@@ -338,7 +338,7 @@ def test_two_threads_share_one_warpdb():
     ["--workload", "topk", "--api"]])
 def test_bench_json_contract(args):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--rows", "2000003", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline"] + args
+           "--full", "--no-cpu-baseline"] + args
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
@@ -357,6 +357,38 @@ def test_bench_json_contract(args):
         assert all(str(v["check"]).startswith("ok") and v["value"] > 0 for v in sec.values()), sec
         assert sec["c4_sum_strong"]["total_rows"] == 3000001 and sec["c4_sum_strong"]["scaling"] == "strong"
         assert sec["c3_group_strong"]["total_rows"] == 2000001 and sec["c3_group_strong"]["scaling"] == "strong"
+
+
+def test_bench_plain_run_dumps_outputs(tmp_path):
+    """A plain run (no --full) times the steps and prints the line with no
+    check, secondary line or CPU baseline; --dump-outputs writes the last
+    timed step's compaction: the count, and a sample (more passing rows than
+    bench.DUMP_SAMPLE) of values with their row ids at the same positions."""
+    n = 4_000_037
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--rows", str(n), "--steps", "3",
+           "--warmup", "1", "--dump-outputs", str(tmp_path / "out")]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=240, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [x for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    # rows/s and the time of one step say the same; ms_per_step is rounded to 1e-4 ms, so within 5e-5 ms of it
+    assert abs(n / line["value"] * 1e3 - line["ms_per_step"]) <= 6e-5
+    assert line["check"] is None and line["cpu_baseline"] is None and "secondary" not in line
+    assert sorted(os.listdir(tmp_path / "out")) == ["count.npy", "row_index.npy", "values.npy"]
+    cols = synth.c2_table(n)
+    passing = cols["price"] > np.float32(15.0)
+    count = np.load(tmp_path / "out" / "count.npy")
+    vals = np.load(tmp_path / "out" / "values.npy")
+    rows = np.load(tmp_path / "out" / "row_index.npy")
+    assert count.dtype == np.float64 and count.tolist() == [float(passing.sum())]
+    assert line["config"]["passing_rows_per_gpu"] == int(passing.sum()) > 2_000_000
+    assert vals.dtype == np.float32 and rows.dtype == np.float64 and len(vals) == len(rows) == 2_000_000
+    ri = rows.astype(np.int64)
+    assert np.array_equal(ri, rows) and ri.min() >= 0 and ri.max() < n
+    assert (np.diff(ri) >= 0).all() and len(np.unique(ri)) > 1_000_000 and passing[ri].all()
+    assert np.array_equal(bits(vals), bits(cols["price"][ri] * cols["quantity"][ri]))
 
 
 @pytest.mark.parametrize("nshards", [2, 3])

@@ -269,7 +269,7 @@ def test_bench_two_ranks_on_one_gpu(workload, extra):
     env = dict(os.environ, WARPDB_DIST_BACKEND="gloo")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--workload", workload, "--steps", "3", "--warmup", "1", *extra],
+                        "--gpus", "2", "--workload", workload, "--steps", "3", "--warmup", "1", "--full", *extra],
                        capture_output=True, text=True, cwd=ROOT, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]

@@ -6,7 +6,7 @@
 #   smoke                      __graft_entry__.smoke()
 #   suite[:PYTEST ARGS]        pytest -m gpu (--durations=25), e.g. suite:-k group
 #   pytest:NAME:FILES          pytest FILES -m gpu -v > NAME.log
-#   bench:NAME[:BENCH ARGS]    python3 bench.py ARGS > NAME.json
+#   bench:NAME[:BENCH ARGS]    python3 bench.py ARGS > NAME.json (--full among ARGS: checks, secondary lines)
 #   prof:NAME[:BENCH ARGS]     the same bench under rocprofv3 --kernel-trace --stats
 #                              (NAME_kernel_stats.csv is the summary to keep)
 #   pmc:NAME[:BENCH ARGS]      FETCH_SIZE and WRITE_SIZE passes (one counter block

@@ -20,9 +20,12 @@ timeout -k 10 900 python3 -u -m pytest tests -m gpu -q -x --timeout 300 --timeou
   > "$O/pytest_gpu.log" 2>&1 || { step "suite FAILED"; exit 1; }
 step smoke
 timeout -k 10 300 python3 -u -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.log" 2>&1 || { step "smoke FAILED"; exit 1; }
-for b in "default:" "sort:--workload sort --no-cpu-baseline" "api_sum:--api --workload sum --no-cpu-baseline" \
-         "api_group:--api --workload group --no-cpu-baseline" "api_topk:--api --workload topk --no-cpu-baseline" \
-         "group_wide:--workload group --keys 1000000 --no-cpu-baseline" "dense:--workload dense --no-cpu-baseline"; do
+for b in "default:--full" "sort:--full --workload sort --no-cpu-baseline" \
+         "api_sum:--full --api --workload sum --no-cpu-baseline" \
+         "api_group:--full --api --workload group --no-cpu-baseline" \
+         "api_topk:--full --api --workload topk --no-cpu-baseline" \
+         "group_wide:--full --workload group --keys 1000000 --no-cpu-baseline" \
+         "dense:--full --workload dense --no-cpu-baseline"; do
   name=${b%%:*}; args=${b#*:}
   step "bench $name"
   timeout -k 10 300 python3 -u bench.py $args > "$O/bench_$name.json" 2> "$O/bench_$name.err" || { step "bench $name FAILED"; exit 1; }
