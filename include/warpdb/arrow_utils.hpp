@@ -2,6 +2,8 @@
 // (reference include/arrow_utils.hpp, src/arrow_utils.cpp:37-94).
 #pragma once
 #include <cstdint>
+#include <string>
+#include <vector>
 
 #include "arrow_c_abi.h"
 
@@ -26,3 +28,10 @@ void export_compact_to_arrow(const float *values, const int64_t *rows, int64_t l
 // ownership of both device buffers passes to the array (release() hipFrees them).
 void export_device_compact_to_arrow(float *d_values, int64_t *d_rows, int64_t length, int device,
                                     ArrowDeviceArray *out, ArrowSchema *schema);
+
+// A multi-column result (query_select) as an Arrow struct array named
+// "result": one float32 child per column, named names[j], then
+// `row: int64`.  Everything is copied into malloc'd memory; the array's
+// release() frees the buffers, the schema's release() the names.
+void export_select_to_arrow(const std::vector<std::string> &names, const std::vector<const float *> &columns,
+                            const int64_t *rows, int64_t length, ArrowArray *out_array, ArrowSchema *out_schema);

@@ -14,8 +14,26 @@
 #include "json_loader.hpp"
 #include "multi_gpu_utils.hpp"
 
+namespace warpdb {
+// A result with several columns (query_select, query_sql_table): column j of
+// result row i is columns[j][i].  `rows` holds the source row id of each
+// result row; it is empty for grouped results.
+struct ResultTable {
+  std::vector<std::string> names;
+  std::vector<std::vector<float>> columns;
+  std::vector<int64_t> rows;
+};
+// Result column names of a SELECT list, without running anything: a bare
+// column keeps its name, an aggregate is agg_kernel() + "_" + its position
+// in the list (from 0: "sum_1"), anything else is "expr" + its position.
+std::vector<std::string> result_column_names(const std::string &sql);
+}  // namespace warpdb
+
 class WarpDB {
  public:
+  using ResultTable = warpdb::ResultTable;
+  // most expressions of one query_select / plain query_sql_table select list
+  static constexpr size_t kMaxSelectExprs = 16;
   // Loads .csv (optional schema; default all Float32) or .json into HBM of
   // `device` and keeps the host copy for query_multi_gpu.
   explicit WarpDB(const std::string &filepath, const std::vector<DataType> &schema = {}, int device = 0);
@@ -67,6 +85,23 @@ class WarpDB {
   // host copy, and zero-copy in HBM (ARROW_DEVICE_ROCM; buffers sized for n_rows).
   void query_arrow_compact(const std::string &expr, ArrowArray *out_array, ArrowSchema *out_schema);
   void query_arrow_device_compact(const std::string &expr, ArrowDeviceArray *out_array, ArrowSchema *out_schema);
+
+  // Multi-column results.  query_select: the expressions' values at the rows
+  // WHERE keeps, in ascending row order, with those rows' ids -- up to four
+  // expressions per pass over the table (one fused ordered compaction: the
+  // columns are read and the WHERE evaluated once), longer lists in
+  // ceil(n / 4) passes; at most kMaxSelectExprs expressions.
+  ResultTable query_select(const std::vector<std::string> &exprs, const std::string &where = "");
+  // SELECT a, b, ... FROM t [WHERE c] [LIMIT n] [OFFSET m]: every select item
+  // as a column, in row order (ORDER BY / DISTINCT over more than one item
+  // are not supported; one item runs as query_sql).  With GROUP BY k: every
+  // item is the key expression or SUM / AVG / COUNT / MIN / MAX of ONE common
+  // value expression, from one grouped pass; HAVING, ORDER BY, LIMIT and
+  // OFFSET as in query_sql; `rows` stays empty.
+  ResultTable query_sql_table(const std::string &sql);
+  // query_select as struct<one float32 child per expression, row: int64>.
+  void query_arrow_select(const std::vector<std::string> &exprs, const std::string &where, ArrowArray *out_array,
+                          ArrowSchema *out_schema);
 
   const Table &table() const { return table_; }
   const HostTable &host_table() const { return host_table_; }

@@ -130,6 +130,31 @@ wx_status wx_project_filter(const wx_table *table, const char *expr, const char 
                             void *d_out_idx, int32_t idx_bytes, int64_t row_base,
                             int64_t *d_count, int64_t *h_count, char *err, size_t errlen);
 
+/* Project + filter with several outputs (a multi-column SELECT): n_exprs
+ * expressions of the same filtered rows in ONE pass -- the columns are read,
+ * the condition evaluated and the rows ranked once.  d_out_vals[j][k]
+ * (each pointer nullable, n_rows entries) = (float)exprs[j] of the k-th
+ * passing row; d_out_idx / idx_bytes / row_base / d_count / h_count as in
+ * wx_project_filter.  n_exprs == 1 is wx_project_filter itself (same module,
+ * any mode); 2 .. WX_MAX_OUTPUTS need WX_MODE_COMPACT (a DENSE mode returns
+ * WX_ERR_UNSUPPORTED).  n_exprs outside 1 .. WX_MAX_OUTPUTS or a blank
+ * expression returns WX_ERR_INVALID.  The expressions and the condition
+ * together may reference at most 16 columns. */
+#define WX_MAX_OUTPUTS 4
+wx_status wx_project_filter_multi(const wx_table *table, const char *const *exprs, int32_t n_exprs,
+                                  const char *cond, const wx_launch *launch, int32_t mode,
+                                  float *const *d_out_vals, void *d_out_idx, int32_t idx_bytes,
+                                  int64_t row_base, int64_t *d_count, int64_t *h_count,
+                                  char *err, size_t errlen);
+/* Build (and cache) the module wx_project_filter_multi would use in
+ * WX_MODE_COMPACT, without launching (works without a GPU, like wx_prepare). */
+wx_status wx_prepare_multi(const wx_table *table, const char *const *exprs, int32_t n_exprs,
+                           const char *cond, const wx_launch *launch, char *err, size_t errlen);
+/* Rows per compaction tile of an n_exprs-output call (it shrinks as the
+ * outputs grow; the diagnostic define list may override it); 0 when n_exprs
+ * is out of range or the geometry is invalid. */
+int32_t wx_select_tile_rows(int32_t n_exprs);
+
 /* SUM((float)expr) over rows where cond holds, accumulated in double.
  * d_out (device, nullable) receives {sum as double, count as int64 bits};
  * h_sum / h_count (host, nullable) synchronise. */

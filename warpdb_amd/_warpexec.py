@@ -61,11 +61,15 @@ def group_list_layout(cap: int):
 MODE_DENSE = 0
 MODE_DENSE_FILL = 1
 MODE_COMPACT = 2
+MAX_OUTPUTS = 4  # WX_MAX_OUTPUTS: expressions of one project_filter_multi call
 
 OP_DENSE, OP_COMPACT, OP_SUM, OP_GROUP, OP_TOPK, OP_UTIL = 0, 1, 2, 3, 4, 5
 
 EXPORTED_SYMBOLS = (
     "wx_project_filter",
+    "wx_project_filter_multi",
+    "wx_prepare_multi",
+    "wx_select_tile_rows",
     "wx_reduce_sum",
     "wx_reduce_stats",
     "wx_group_sum",
@@ -148,6 +152,9 @@ def load() -> ctypes.CDLL:
     pI64, pD = ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_double)
     sig = {
         "wx_project_filter": [T, E, E, L, I32, P, P, I32, I64, P, pI64, E, S],
+        "wx_project_filter_multi": [T, ctypes.POINTER(E), I32, E, L, I32, ctypes.POINTER(P), P, I32, I64, P, pI64, E,
+                                    S],
+        "wx_prepare_multi": [T, ctypes.POINTER(E), I32, E, L, E, S],
         "wx_reduce_sum": [T, E, E, L, P, pD, pI64, E, S],
         "wx_reduce_stats": [T, E, E, L, P, ctypes.POINTER(WxStats), E, S],
         "wx_group_sum": [T, E, E, E, L, I32, I64, P, P, P, P, pI64, E, S],
@@ -182,6 +189,8 @@ def load() -> ctypes.CDLL:
     lib.wx_cache_stats.restype = None
     lib.wx_shutdown.argtypes = []
     lib.wx_shutdown.restype = None
+    lib.wx_select_tile_rows.argtypes = [I32]
+    lib.wx_select_tile_rows.restype = ctypes.c_int32
     lib.wx_abi_version.argtypes = []
     lib.wx_abi_version.restype = ctypes.c_int32
     _lib = lib
@@ -256,6 +265,44 @@ def project_filter(table: Table, expr: str, cond: Optional[str], launch: WxLaunc
                                ctypes.byref(h) if want_count else None, err, len(err))
     _check(st, err)
     return h.value if want_count else None
+
+
+def _expr_array(exprs: Sequence[Optional[str]]):
+    return (ctypes.c_char_p * max(1, len(exprs)))(*[_enc(e) for e in exprs])
+
+
+def project_filter_multi(table: Table, exprs: Sequence[str], cond: Optional[str], launch: WxLaunch,
+                         d_out_vals: Sequence[int], d_out_idx: int = 0, idx_bytes: int = 8, row_base: int = 0,
+                         d_count: int = 0, want_count: bool = False, mode: int = MODE_COMPACT) -> Optional[int]:
+    """len(exprs) outputs of one filtered result in one pass (ordered
+    compaction): d_out_vals[j] (0 = not wanted) receives expression j of the
+    passing rows, d_out_idx their row ids.  A shorter d_out_vals is padded
+    with nulls."""
+    lib = load()
+    err = _err()
+    h = ctypes.c_int64(-1)
+    outs = list(d_out_vals) + [0] * (len(exprs) - len(d_out_vals))
+    ptrs = (ctypes.c_void_p * max(1, len(outs)))(*[p or None for p in outs])
+    st = lib.wx_project_filter_multi(ctypes.byref(table.c), _expr_array(exprs), len(exprs), _enc(cond),
+                                     ctypes.byref(launch), mode, ptrs, d_out_idx or None, idx_bytes, row_base,
+                                     d_count or None, ctypes.byref(h) if want_count else None, err, len(err))
+    _check(st, err)
+    return h.value if want_count else None
+
+
+def prepare_multi(table: Table, exprs: Sequence[str], cond: Optional[str] = None,
+                  launch: Optional[WxLaunch] = None) -> None:
+    """Compile the module project_filter_multi would use (no GPU needed)."""
+    lib = load()
+    err = _err()
+    L = launch or make_launch()
+    _check(lib.wx_prepare_multi(ctypes.byref(table.c), _expr_array(exprs), len(exprs), _enc(cond), ctypes.byref(L),
+                                err, len(err)), err)
+
+
+def select_tile_rows(n_exprs: int) -> int:
+    """Rows per compaction tile of an n_exprs-output call (0: out of range)."""
+    return int(load().wx_select_tile_rows(n_exprs))
 
 
 def reduce_sum(table: Table, expr: str, cond: Optional[str], launch: WxLaunch, d_out: int = 0,

@@ -9,6 +9,7 @@
 #include <unistd.h>
 
 #include <cstdlib>
+#include <memory>
 #include <vector>
 #include <cstring>
 #include <new>
@@ -199,7 +200,104 @@ void fill_compact_array(CompactResult *r, int64_t length, ArrowArray *a) {
   a->private_data = r;
 }
 
+// struct<one float32 child per column, row: int64> of a multi-column
+// result: like CompactResult with any number of value children.  The parent
+// owns every child, its buffer (malloc) and its name.
+struct SelectResult {
+  std::vector<void *> data;                 // one buffer per child (values..., rows)
+  std::vector<const void *> leaf_buffers;   // two entries per child: {no validity bitmap, data}
+  const void *parent_buffers[1] = {nullptr};
+  std::vector<ArrowArray> child_arrays;
+  std::vector<ArrowArray *> children;
+};
+
+void release_select_array(ArrowArray *a) {
+  if (!a || !a->release) return;
+  auto *r = static_cast<SelectResult *>(a->private_data);
+  if (r) {
+    for (auto &ch : r->child_arrays)
+      if (ch.release) ch.release(&ch);
+    for (void *p : r->data) std::free(p);
+    delete r;
+  }
+  a->release = nullptr;
+}
+
+struct SelectSchema {
+  std::vector<std::string> names;
+  std::vector<ArrowSchema> child_schemas;
+  std::vector<ArrowSchema *> children;
+};
+
+void release_select_schema(ArrowSchema *s) {
+  if (!s || !s->release) return;
+  auto *c = static_cast<SelectSchema *>(s->private_data);
+  if (c) {
+    for (auto &ch : c->child_schemas)
+      if (ch.release) ch.release(&ch);
+    delete c;
+  }
+  s->release = nullptr;
+}
+
 }  // namespace
+
+void export_select_to_arrow(const std::vector<std::string> &names, const std::vector<const float *> &columns,
+                            const int64_t *rows, int64_t length, ArrowArray *out_array, ArrowSchema *out_schema) {
+  if (!out_array || !out_schema) throw std::invalid_argument("Null output");
+  if (length < 0) throw std::invalid_argument("negative length");
+  if (names.size() != columns.size()) throw std::invalid_argument("names and columns differ in number");
+  const size_t n = static_cast<size_t>(length), m = columns.size();
+  auto r = std::unique_ptr<SelectResult>(new SelectResult());
+  auto c = std::unique_ptr<SelectSchema>(new SelectSchema());
+  // every vector gets its final size first: the arrays point into them
+  r->data.assign(m + 1, nullptr);
+  r->leaf_buffers.assign(2 * (m + 1), nullptr);
+  r->child_arrays.resize(m + 1);
+  r->children.resize(m + 1);
+  c->names = names;
+  c->names.push_back("row");
+  c->child_schemas.resize(m + 1);
+  c->children.resize(m + 1);
+  try {
+    for (size_t j = 0; j <= m; ++j) {
+      const size_t width = j < m ? sizeof(float) : sizeof(int64_t);
+      r->data[j] = std::malloc(n * width + 1);
+      if (!r->data[j]) throw std::bad_alloc();
+      const void *src = j < m ? static_cast<const void *>(columns[j]) : static_cast<const void *>(rows);
+      if (n) std::memcpy(r->data[j], src, n * width);
+    }
+  } catch (...) {
+    for (void *p : r->data) std::free(p);
+    throw;
+  }
+  for (size_t j = 0; j <= m; ++j) {
+    r->leaf_buffers[2 * j + 1] = r->data[j];
+    fill_leaf_array(&r->child_arrays[j], &r->leaf_buffers[2 * j], length);
+    r->children[j] = &r->child_arrays[j];
+    fill_leaf_schema(&c->child_schemas[j], j < m ? "f" : "l", c->names[j].c_str(), 0);
+    c->children[j] = &c->child_schemas[j];
+  }
+  out_array->length = length;
+  out_array->null_count = 0;
+  out_array->offset = 0;
+  out_array->n_buffers = 1;  // struct: validity bitmap only (none)
+  out_array->n_children = static_cast<int64_t>(m + 1);
+  out_array->buffers = r->parent_buffers;
+  out_array->children = r->children.data();
+  out_array->dictionary = nullptr;
+  out_array->release = release_select_array;
+  out_array->private_data = r.release();
+  out_schema->format = "+s";
+  out_schema->name = "result";
+  out_schema->metadata = nullptr;
+  out_schema->flags = 0;
+  out_schema->n_children = static_cast<int64_t>(m + 1);
+  out_schema->children = c->children.data();
+  out_schema->dictionary = nullptr;
+  out_schema->release = release_select_schema;
+  out_schema->private_data = c.release();
+}
 
 void export_compact_to_arrow(const float *values, const int64_t *rows, int64_t length, ArrowArray *out_array,
                              ArrowSchema *out_schema) {

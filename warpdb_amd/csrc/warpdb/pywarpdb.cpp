@@ -53,6 +53,13 @@ py::tuple topk_arrays(const warpdb::TopkResult &t) {
                         py::array_t<float>(static_cast<py::ssize_t>(t.values.size()), t.values.data()));
 }
 
+// (names, [float32 array per column], int64 source rows)
+py::tuple table_arrays(const warpdb::ResultTable &t) {
+  py::list cols;
+  for (const auto &c : t.columns) cols.append(py::array_t<float>(static_cast<py::ssize_t>(c.size()), c.data()));
+  return py::make_tuple(t.names, cols, py::array_t<int64_t>(static_cast<py::ssize_t>(t.rows.size()), t.rows.data()));
+}
+
 py::tuple device_capsules(ArrowDeviceArray *arr, ArrowSchema *schema) {
   // named as the Arrow PyCapsule interface names device arrays
   py::capsule a(arr, "arrow_device_array", [](PyObject *o) {
@@ -162,6 +169,40 @@ PYBIND11_MODULE(pywarpdb, m) {
           },
           py::arg("expr"), "Passing rows as struct<value, row> in HBM (ArrowDeviceArray capsule, ROCm).")
       .def("query_compact", &WarpDB::query_compact, py::call_guard<py::gil_scoped_release>())
+      .def(
+          "query_select",
+          [](WarpDB &db, const std::vector<std::string> &exprs, const std::string &where) {
+            warpdb::ResultTable t;
+            {
+              py::gil_scoped_release nogil;
+              t = db.query_select(exprs, where);
+            }
+            return table_arrays(t);
+          },
+          py::arg("exprs"), py::arg("where") = "",
+          "Several expressions of the rows WHERE keeps, in row order (fused passes of up to four) -> "
+          "(names, [float32 arrays], int64 rows).")
+      .def(
+          "query_sql_table",
+          [](WarpDB &db, const std::string &sql) {
+            warpdb::ResultTable t;
+            {
+              py::gil_scoped_release nogil;
+              t = db.query_sql_table(sql);
+            }
+            return table_arrays(t);
+          },
+          py::arg("sql"),
+          "SELECT with several items (plain, or GROUP BY key + aggregates of one expression) -> "
+          "(names, [float32 arrays], int64 rows; rows empty for grouped results).")
+      .def(
+          "query_arrow_select",
+          [](WarpDB &db, const std::vector<std::string> &exprs, const std::string &where) {
+            return export_with<ArrowArray>(
+                [&](ArrowArray *a, ArrowSchema *s) { db.query_arrow_select(exprs, where, a, s); }, arrow_capsules);
+          },
+          py::arg("exprs"), py::arg("where") = "",
+          "query_select as struct<one float32 child per expression, row: int64> (Arrow C Data Interface capsules).")
       .def("query_sum", &WarpDB::query_sum, py::call_guard<py::gil_scoped_release>())
       .def("query_multi_gpu_sum", &WarpDB::query_multi_gpu_sum, py::call_guard<py::gil_scoped_release>())
       .def(
@@ -333,6 +374,8 @@ PYBIND11_MODULE(pywarpdb, m) {
       "Host-side CSV load (load_csv_to_host) as {column: numpy array | list}; no GPU needed.");
 
   // front end, for tests and tools
+  m.def("result_column_names", &warpdb::result_column_names, py::arg("sql"),
+        "Result column names of a SELECT list (no table, no GPU).");
   m.def("lower_expression", [](const std::string &e) { return parse_expression(tokenize(e))->to_cuda_expr(); });
   m.def("split_where", [](const std::string &q) {
     std::string e, c;

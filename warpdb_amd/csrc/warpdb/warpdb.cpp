@@ -447,6 +447,122 @@ bool uses_minmax(const ASTNode *n) {
   if (auto b = dynamic_cast<const BinaryOpNode *>(n)) return uses_minmax(b->left.get()) || uses_minmax(b->right.get());
   return false;
 }
+
+// One grouped query's wx_group_agg call and the host-side ordering of its
+// groups (HAVING, then ORDER BY; they arrive in ascending key order), shared
+// by query_sql and query_sql_table.  `val` is the aggregated expression.
+struct GroupRun {
+  std::vector<int32_t> keys;
+  std::vector<double> sums;
+  std::vector<int64_t> cnts;
+  std::vector<float> mins, maxs;  // MIN / MAX builds only
+  std::vector<size_t> order;      // the groups HAVING keeps, in result order
+  // per-group aggregate value (AggData, src/warpdb.cpp:375-385)
+  double value_of(AggregationType t, size_t i) const {
+    switch (t) {
+      case AggregationType::Sum: return sums[i];
+      case AggregationType::Avg: return sums[i] / static_cast<double>(cnts[i]);
+      case AggregationType::Count: return static_cast<double>(cnts[i]);
+      case AggregationType::Min: return mins[i];
+      case AggregationType::Max: return maxs[i];
+    }
+    return NAN;
+  }
+};
+
+GroupRun run_grouped(const Table &table, const QueryAST &ast, const ASTNode *val, bool select_minmax,
+                     const std::string &cond) {
+  WxTableView v(table);
+  wx_launch L = sync_launch(table.device);
+  char err[8192];
+  if (ast.group_by->keys.size() != 1) throw std::runtime_error("GROUP BY supports one key expression");
+  const ASTNode *key = ast.group_by->keys[0].get();
+  const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(table.num_rows, 1 << 22));
+  // MIN / MAX anywhere (SELECT, HAVING, ORDER BY) selects the MIN / MAX build
+  const bool mm = select_minmax || (ast.having && uses_minmax(ast.having->get())) ||
+                  (ast.order_by && uses_minmax(ast.order_by->expr.get()));
+  DeviceBuffer dk(table.device, cap * 4), ds(table.device, cap * 8), dc(table.device, cap * 8);
+  DeviceBuffer dmn(table.device, mm ? cap * 4 : 4), dmx(table.device, mm ? cap * 4 : 4);
+  int64_t g = 0;
+  // WARPDB_GROUP_ROW_ORDER=1: each group's sum folded in row order, the
+  // reference's own fold (src/warpdb.cpp:373-385) to the bit (WX_F_ROW_ORDER)
+  const char *ro = std::getenv("WARPDB_GROUP_ROW_ORDER");
+  if (ro && std::string(ro) == "1") L.flags |= WX_F_ROW_ORDER;
+  throw_on(wx_group_agg(&v.table, val->to_cuda_expr().c_str(), key->to_cuda_expr().c_str(), cond.c_str(), &L,
+                        0, cap, static_cast<int32_t *>(dk.ptr), static_cast<double *>(ds.ptr),
+                        static_cast<int64_t *>(dc.ptr), mm ? static_cast<float *>(dmn.ptr) : nullptr,
+                        mm ? static_cast<float *>(dmx.ptr) : nullptr, nullptr, &g, err, sizeof(err)),
+           err);
+  GroupRun run;
+  std::vector<int32_t> &keys = run.keys;
+  std::vector<double> &sums = run.sums;
+  std::vector<int64_t> &cnts = run.cnts;
+  std::vector<float> &mins = run.mins, &maxs = run.maxs;
+  keys.resize(g);
+  sums.resize(g);
+  cnts.resize(g);
+  mins.resize(mm ? g : 0);
+  maxs.resize(mm ? g : 0);
+  {
+    DevGuard dg(table.device);
+    if (g) {
+      hip_ok(hipMemcpy(keys.data(), dk.ptr, g * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+      hip_ok(hipMemcpy(sums.data(), ds.ptr, g * 8, hipMemcpyDeviceToHost), "hipMemcpy");
+      hip_ok(hipMemcpy(cnts.data(), dc.ptr, g * 8, hipMemcpyDeviceToHost), "hipMemcpy");
+      if (mm) {
+        hip_ok(hipMemcpy(mins.data(), dmn.ptr, g * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+        hip_ok(hipMemcpy(maxs.data(), dmx.ptr, g * 4, hipMemcpyDeviceToHost), "hipMemcpy");
+      }
+    }
+  }
+  auto value_of = [&](AggregationType t, size_t i) { return run.value_of(t, i); };
+  // HAVING over the (few) aggregated groups, with the reference's
+  // comparison semantics (src/warpdb.cpp:387-423)
+  std::function<double(const ASTNode *, size_t)> having = [&](const ASTNode *n, size_t i) -> double {
+    if (auto c = dynamic_cast<const ConstantNode *>(n)) return std::stod(c->value);
+    if (auto a = dynamic_cast<const AggregationNode *>(n)) {
+      if (!same_expr(a->expr.get(), val) && a->agg != AggregationType::Count)
+        throw std::runtime_error("HAVING may only aggregate the selected expression");
+      return value_of(a->agg, i);
+    }
+    if (auto b = dynamic_cast<const BinaryOpNode *>(n)) {
+      const double l = having(b->left.get(), i), r = having(b->right.get(), i);
+      const std::string &op = b->op;
+      if (op == "+") return l + r;
+      if (op == "-") return l - r;
+      if (op == "*") return l * r;
+      if (op == "/") return l / r;
+      if (op == ">") return l > r;
+      if (op == "<") return l < r;
+      if (op == ">=") return l >= r;
+      if (op == "<=") return l <= r;
+      if (op == "==") return l == r;
+      if (op == "!=") return l != r;
+      if (op == "&&") return l != 0 && r != 0;
+      if (op == "||") return l != 0 || r != 0;
+    }
+    if (same_expr(n, key)) return keys[i];
+    throw std::runtime_error("unsupported HAVING term");
+  };
+  std::vector<size_t> &order = run.order;
+  for (size_t i = 0; i < static_cast<size_t>(g); ++i)
+    if (!ast.having || having(ast.having->get(), i) != 0.0) order.push_back(i);
+  if (ast.order_by) {  // groups arrive in ascending key order
+    const ASTNode *ob = ast.order_by->expr.get();
+    auto *oagg = dynamic_cast<const AggregationNode *>(ob);
+    if (oagg) {
+      std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+        const double x = value_of(oagg->agg, a), y = value_of(oagg->agg, b);
+        return ast.order_by->ascending ? x < y : x > y;
+      });
+    } else if (same_expr(ob, key)) {
+      if (!ast.order_by->ascending) std::reverse(order.begin(), order.end());
+    } else {
+      throw std::runtime_error("ORDER BY with GROUP BY must name the key or an aggregate");
+    }
+  }
+  return run;
+}
 }  // namespace
 
 std::vector<float> WarpDB::query_sql(const std::string &sql) {
@@ -490,97 +606,8 @@ std::vector<float> WarpDB::query_sql(const std::string &sql) {
 
   if (ast.group_by) {
     if (!agg) throw std::runtime_error("Only aggregation queries supported with GROUP BY");
-    if (ast.group_by->keys.size() != 1) throw std::runtime_error("GROUP BY supports one key expression");
-    const ASTNode *key = ast.group_by->keys[0].get();
-    const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(table_.num_rows, 1 << 22));
-    // MIN / MAX anywhere (SELECT, HAVING, ORDER BY) selects the MIN / MAX build
-    const bool mm = uses_minmax(agg) || (ast.having && uses_minmax(ast.having->get())) ||
-                    (ast.order_by && uses_minmax(ast.order_by->expr.get()));
-    DeviceBuffer dk(table_.device, cap * 4), ds(table_.device, cap * 8), dc(table_.device, cap * 8);
-    DeviceBuffer dmn(table_.device, mm ? cap * 4 : 4), dmx(table_.device, mm ? cap * 4 : 4);
-    int64_t g = 0;
-    // WARPDB_GROUP_ROW_ORDER=1: each group's sum folded in row order, the
-    // reference's own fold (src/warpdb.cpp:373-385) to the bit (WX_F_ROW_ORDER)
-    const char *ro = std::getenv("WARPDB_GROUP_ROW_ORDER");
-    if (ro && std::string(ro) == "1") L.flags |= WX_F_ROW_ORDER;
-    throw_on(wx_group_agg(&v.table, agg->expr->to_cuda_expr().c_str(), key->to_cuda_expr().c_str(), cond.c_str(), &L,
-                          0, cap, static_cast<int32_t *>(dk.ptr), static_cast<double *>(ds.ptr),
-                          static_cast<int64_t *>(dc.ptr), mm ? static_cast<float *>(dmn.ptr) : nullptr,
-                          mm ? static_cast<float *>(dmx.ptr) : nullptr, nullptr, &g, err, sizeof(err)),
-             err);
-    std::vector<int32_t> keys(g);
-    std::vector<double> sums(g);
-    std::vector<int64_t> cnts(g);
-    std::vector<float> mins(mm ? g : 0), maxs(mm ? g : 0);
-    {
-      DevGuard dg(table_.device);
-      if (g) {
-        hip_ok(hipMemcpy(keys.data(), dk.ptr, g * 4, hipMemcpyDeviceToHost), "hipMemcpy");
-        hip_ok(hipMemcpy(sums.data(), ds.ptr, g * 8, hipMemcpyDeviceToHost), "hipMemcpy");
-        hip_ok(hipMemcpy(cnts.data(), dc.ptr, g * 8, hipMemcpyDeviceToHost), "hipMemcpy");
-        if (mm) {
-          hip_ok(hipMemcpy(mins.data(), dmn.ptr, g * 4, hipMemcpyDeviceToHost), "hipMemcpy");
-          hip_ok(hipMemcpy(maxs.data(), dmx.ptr, g * 4, hipMemcpyDeviceToHost), "hipMemcpy");
-        }
-      }
-    }
-    // per-group aggregate value (AggData, src/warpdb.cpp:375-385)
-    auto value_of = [&](AggregationType t, size_t i) -> double {
-      switch (t) {
-        case AggregationType::Sum: return sums[i];
-        case AggregationType::Avg: return sums[i] / static_cast<double>(cnts[i]);
-        case AggregationType::Count: return static_cast<double>(cnts[i]);
-        case AggregationType::Min: return mins[i];
-        case AggregationType::Max: return maxs[i];
-      }
-      return NAN;
-    };
-    // HAVING over the (few) aggregated groups, with the reference's
-    // comparison semantics (src/warpdb.cpp:387-423)
-    std::function<double(const ASTNode *, size_t)> having = [&](const ASTNode *n, size_t i) -> double {
-      if (auto c = dynamic_cast<const ConstantNode *>(n)) return std::stod(c->value);
-      if (auto a = dynamic_cast<const AggregationNode *>(n)) {
-        if (!same_expr(a->expr.get(), agg->expr.get()) && a->agg != AggregationType::Count)
-          throw std::runtime_error("HAVING may only aggregate the selected expression");
-        return value_of(a->agg, i);
-      }
-      if (auto b = dynamic_cast<const BinaryOpNode *>(n)) {
-        const double l = having(b->left.get(), i), r = having(b->right.get(), i);
-        const std::string &op = b->op;
-        if (op == "+") return l + r;
-        if (op == "-") return l - r;
-        if (op == "*") return l * r;
-        if (op == "/") return l / r;
-        if (op == ">") return l > r;
-        if (op == "<") return l < r;
-        if (op == ">=") return l >= r;
-        if (op == "<=") return l <= r;
-        if (op == "==") return l == r;
-        if (op == "!=") return l != r;
-        if (op == "&&") return l != 0 && r != 0;
-        if (op == "||") return l != 0 || r != 0;
-      }
-      if (same_expr(n, key)) return keys[i];
-      throw std::runtime_error("unsupported HAVING term");
-    };
-    std::vector<size_t> order;
-    for (size_t i = 0; i < static_cast<size_t>(g); ++i)
-      if (!ast.having || having(ast.having->get(), i) != 0.0) order.push_back(i);
-    if (ast.order_by) {  // groups arrive in ascending key order
-      const ASTNode *ob = ast.order_by->expr.get();
-      auto *oagg = dynamic_cast<const AggregationNode *>(ob);
-      if (oagg) {
-        std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-          const double x = value_of(oagg->agg, a), y = value_of(oagg->agg, b);
-          return ast.order_by->ascending ? x < y : x > y;
-        });
-      } else if (same_expr(ob, key)) {
-        if (!ast.order_by->ascending) std::reverse(order.begin(), order.end());
-      } else {
-        throw std::runtime_error("ORDER BY with GROUP BY must name the key or an aggregate");
-      }
-    }
-    for (size_t i : order) result.push_back(static_cast<float>(value_of(agg->agg, i)));
+    const GroupRun r = run_grouped(table_, ast, agg->expr.get(), uses_minmax(agg), cond);
+    for (size_t i : r.order) result.push_back(static_cast<float>(r.value_of(agg->agg, i)));
     if (ast.distinct) {
       std::sort(result.begin(), result.end());
       result.erase(std::unique(result.begin(), result.end()), result.end());
@@ -675,4 +702,217 @@ std::vector<float> WarpDB::query_sql(const std::string &sql) {
   result = download(dv.ptr, count, table_.device);
   if (ast.distinct) result.erase(std::unique(result.begin(), result.end()), result.end());
   return slice(std::move(result));
+}
+
+// ------------------------------------------------- multi-column results
+namespace {
+std::string column_name(const ASTNode *n, size_t pos) {
+  if (auto v = dynamic_cast<const VariableNode *>(n)) return v->name;
+  if (auto a = dynamic_cast<const AggregationNode *>(n)) return a->agg_kernel() + "_" + std::to_string(pos);
+  return "expr" + std::to_string(pos);
+}
+
+// The lowered expressions' values at the rows `cond` keeps, in row order,
+// and those rows' ids: up to WX_MAX_OUTPUTS expressions per fused pass, the
+// same WHERE in every pass; only the first pass writes the row ids, and the
+// passes' counts must agree.  At most max_rows rows are downloaded.
+void select_run(const Table &table, const std::vector<std::string> &exprs_c, const std::string &cond_c,
+                int64_t max_rows, warpdb::ResultTable &out) {
+  const int64_t n = table.num_rows;
+  const size_t m = exprs_c.size();
+  const size_t width = std::min<size_t>(m, WX_MAX_OUTPUTS);
+  std::vector<std::unique_ptr<DeviceBuffer>> vals;
+  for (size_t j = 0; j < width; ++j)
+    vals.push_back(std::make_unique<DeviceBuffer>(table.device, sizeof(float) * static_cast<size_t>(n ? n : 1)));
+  DeviceBuffer idx(table.device, sizeof(int64_t) * static_cast<size_t>(n ? n : 1));
+  WxTableView v(table);
+  wx_launch L = sync_launch(table.device);
+  char err[8192];
+  int64_t count = 0, keep = 0;
+  out.columns.clear();
+  for (size_t first = 0; first < m; first += WX_MAX_OUTPUTS) {
+    const size_t k = std::min<size_t>(WX_MAX_OUTPUTS, m - first);
+    const char *ex[WX_MAX_OUTPUTS] = {nullptr, nullptr, nullptr, nullptr};
+    float *dst[WX_MAX_OUTPUTS] = {nullptr, nullptr, nullptr, nullptr};
+    for (size_t j = 0; j < k; ++j) {
+      ex[j] = exprs_c[first + j].c_str();
+      dst[j] = static_cast<float *>(vals[j]->ptr);
+    }
+    int64_t c = 0;
+    throw_on(wx_project_filter_multi(&v.table, ex, static_cast<int32_t>(k), cond_c.c_str(), &L, WX_MODE_COMPACT, dst,
+                                     first == 0 ? idx.ptr : nullptr, 8, 0, nullptr, &c, err, sizeof(err)),
+             err);
+    if (first == 0) {
+      count = c;
+      keep = std::min(count, max_rows);
+      out.rows.assign(static_cast<size_t>(keep), 0);
+      DevGuard g(table.device);
+      if (keep) hip_ok(hipMemcpy(out.rows.data(), idx.ptr, sizeof(int64_t) * keep, hipMemcpyDeviceToHost), "hipMemcpy");
+    } else if (c != count) {
+      throw std::runtime_error("multi-column SELECT: the passes' row counts disagree");
+    }
+    for (size_t j = 0; j < k; ++j) out.columns.push_back(download(vals[j]->ptr, keep, table.device));
+  }
+}
+}  // namespace
+
+std::vector<std::string> warpdb::result_column_names(const std::string &sql) {
+  QueryAST ast;
+  try {
+    ast = parse_query(tokenize(sql));
+  } catch (const std::exception &e) {
+    throw std::runtime_error(std::string("Failed to parse SQL: ") + e.what());
+  }
+  std::vector<std::string> names;
+  for (size_t i = 0; i < ast.select_list.size(); ++i) names.push_back(column_name(ast.select_list[i].get(), i));
+  return names;
+}
+
+WarpDB::ResultTable WarpDB::query_select(const std::vector<std::string> &exprs, const std::string &where) {
+  if (exprs.empty()) throw std::runtime_error("Empty SELECT list");
+  if (exprs.size() > kMaxSelectExprs)
+    throw std::runtime_error("query_select takes at most " + std::to_string(kMaxSelectExprs) + " expressions");
+  const auto cols = names_of(table_);
+  ResultTable out;
+  std::vector<std::string> lowered;
+  for (size_t i = 0; i < exprs.size(); ++i) {
+    if (blank(exprs[i])) throw std::runtime_error("Empty query expression");
+    ASTNodePtr ex;
+    try {
+      ex = parse_expression(tokenize(exprs[i]));
+    } catch (const std::exception &err) {
+      throw std::runtime_error(std::string("Failed to parse expression: ") + err.what());
+    }
+    validate_ast(ex.get(), cols);
+    if (dynamic_cast<const AggregationNode *>(ex.get()))
+      throw std::runtime_error("query_select takes plain expressions, not aggregates");
+    lowered.push_back(ex->to_cuda_expr());
+    out.names.push_back(column_name(ex.get(), i));
+  }
+  std::string cond_c;
+  if (!blank(where)) {
+    try {
+      auto cx = parse_expression(tokenize(where));
+      validate_ast(cx.get(), cols);
+      cond_c = cx->to_cuda_expr();
+    } catch (const std::exception &err) {
+      throw std::runtime_error(std::string("Failed to parse WHERE clause: ") + err.what());
+    }
+  }
+  select_run(table_, lowered, cond_c, table_.num_rows, out);
+  return out;
+}
+
+void WarpDB::query_arrow_select(const std::vector<std::string> &exprs, const std::string &where,
+                                ArrowArray *out_array, ArrowSchema *out_schema) {
+  const ResultTable r = query_select(exprs, where);
+  std::vector<const float *> columns;
+  for (const auto &c : r.columns) columns.push_back(c.data());
+  export_select_to_arrow(r.names, columns, r.rows.data(), static_cast<int64_t>(r.rows.size()), out_array, out_schema);
+}
+
+WarpDB::ResultTable WarpDB::query_sql_table(const std::string &sql) {
+  QueryAST ast;
+  try {
+    ast = parse_query(tokenize(sql));
+  } catch (const std::exception &e) {
+    throw std::runtime_error(std::string("Failed to parse SQL: ") + e.what());
+  }
+  const auto cols = names_of(table_);
+  auto validate_ctx = [&](const ASTNode *n, const std::string &ctx) {
+    try {
+      validate_ast(n, cols);
+    } catch (const std::exception &e) {
+      throw std::runtime_error(ctx + ": " + e.what());
+    }
+  };
+  if (ast.select_list.empty()) throw std::runtime_error("Empty SELECT list");
+  for (const auto &e : ast.select_list) validate_ctx(e.get(), "SELECT clause");
+  for (const auto &j : ast.joins) validate_ctx(j.condition.get(), "JOIN condition");
+  if (ast.where) validate_ctx(ast.where->get(), "WHERE clause");
+  if (ast.group_by)
+    for (const auto &k : ast.group_by->keys) validate_ctx(k.get(), "GROUP BY");
+  if (ast.order_by) validate_ctx(ast.order_by->expr.get(), "ORDER BY");
+  if (!ast.joins.empty()) throw std::runtime_error("JOIN is not supported by the execution engine");
+
+  const size_t m = ast.select_list.size();
+  ResultTable out;
+  for (size_t i = 0; i < m; ++i) out.names.push_back(column_name(ast.select_list[i].get(), i));
+  const std::string cond = ast.where ? (*ast.where)->to_cuda_expr() : std::string();
+  const size_t off = ast.offset ? static_cast<size_t>(std::max(0, ast.offset->count)) : 0;
+  const size_t lim = ast.limit ? static_cast<size_t>(std::max(0, ast.limit->count)) : SIZE_MAX;
+  auto slice = [&](auto &r) {
+    if (off >= r.size()) {
+      r.clear();
+      return;
+    }
+    r.erase(r.begin(), r.begin() + static_cast<long>(off));
+    if (r.size() > lim) r.resize(lim);
+  };
+  auto is_agg = [](const ASTNode *n) { return dynamic_cast<const AggregationNode *>(n) != nullptr; };
+  for (const auto &e : ast.select_list)
+    if (dynamic_cast<const WindowFunctionNode *>(e.get()))
+      throw std::runtime_error("window functions are not supported by the execution engine");
+
+  // one item that query_sql answers whole: an aggregate, or an ordered /
+  // distinct projection (no row ids: the rows are aggregated or permuted)
+  if (m == 1 && (is_agg(ast.select_list[0].get()) || (!ast.group_by && (ast.order_by || ast.distinct)))) {
+    out.columns.push_back(query_sql(sql));
+    return out;
+  }
+
+  if (ast.group_by) {
+    if (ast.group_by->keys.size() != 1) throw std::runtime_error("GROUP BY supports one key expression");
+    if (ast.distinct) throw std::runtime_error("DISTINCT over a multi-column result is not supported");
+    const ASTNode *key = ast.group_by->keys[0].get();
+    // every item: the key, or an aggregate of the one common value expression
+    // (COUNT counts the group's rows whatever it names)
+    const ASTNode *val = nullptr, *counted = nullptr;
+    bool mm = false;
+    for (size_t i = 0; i < m; ++i) {
+      const ASTNode *item = ast.select_list[i].get();
+      if (auto a = dynamic_cast<const AggregationNode *>(item)) {
+        mm = mm || uses_minmax(a);
+        if (a->agg == AggregationType::Count) {
+          if (!counted) counted = a->expr.get();
+        } else if (!val) {
+          val = a->expr.get();
+        } else if (!same_expr(val, a->expr.get())) {
+          throw std::runtime_error("GROUP BY select list aggregates two different expressions (" +
+                                   val->to_cuda_expr() + " and " + a->expr->to_cuda_expr() + "): one is supported");
+        }
+      } else if (!same_expr(item, key)) {
+        throw std::runtime_error("select item " + std::to_string(i) +
+                                 " must be the GROUP BY key or an aggregate (SUM / AVG / COUNT / MIN / MAX)");
+      }
+    }
+    if (!val) val = counted ? counted : key;
+    const GroupRun r = run_grouped(table_, ast, val, mm, cond);
+    out.columns.assign(m, std::vector<float>());
+    for (size_t j = 0; j < m; ++j) {
+      auto a = dynamic_cast<const AggregationNode *>(ast.select_list[j].get());
+      for (size_t i : r.order)
+        out.columns[j].push_back(a ? static_cast<float>(r.value_of(a->agg, i)) : static_cast<float>(r.keys[i]));
+      slice(out.columns[j]);
+    }
+    return out;
+  }
+
+  for (const auto &e : ast.select_list)
+    if (is_agg(e.get()))
+      throw std::runtime_error("aggregates beside other select items need GROUP BY: not supported");
+  if (ast.order_by || ast.distinct)
+    throw std::runtime_error("ORDER BY / DISTINCT over a multi-column result is not supported (row order only)");
+  if (m > kMaxSelectExprs)
+    throw std::runtime_error("a select list takes at most " + std::to_string(kMaxSelectExprs) + " expressions");
+  std::vector<std::string> lowered;
+  for (const auto &e : ast.select_list) lowered.push_back(e->to_cuda_expr());
+  // row order: only the first OFFSET + LIMIT rows are downloaded
+  const int64_t want = !ast.limit ? table_.num_rows
+                                  : static_cast<int64_t>(std::min<size_t>(static_cast<size_t>(table_.num_rows),
+                                                                          off + std::min(lim, SIZE_MAX - off)));
+  select_run(table_, lowered, cond, want, out);
+  for (auto &c : out.columns) slice(c);
+  slice(out.rows);
+  return out;
 }
