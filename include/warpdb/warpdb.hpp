@@ -103,6 +103,31 @@ class WarpDB {
   void query_arrow_select(const std::vector<std::string> &exprs, const std::string &where, ArrowArray *out_array,
                           ArrowSchema *out_schema);
 
+  // Ordered multi-column results: the expressions' values at the rows WHERE
+  // keeps, ordered by one key expression (NaN keys last in both directions,
+  // ties by ascending row), with those rows' ids.  The sorted row ids are
+  // computed once (a top-K scan for OFFSET + LIMIT <= 32, else a key
+  // compaction and a pair sort), then the expressions are gathered at them,
+  // four per pass; only OFFSET + LIMIT rows are computed and downloaded.
+  // limit < 0: no limit.  At most kMaxSelectExprs expressions, validated and
+  // named as in query_select.
+  ResultTable query_select_ordered(const std::vector<std::string> &exprs, const std::string &where,
+                                   const std::string &order_by, bool descending = false, int64_t limit = -1,
+                                   int64_t offset = 0);
+  // Late materialisation: the expressions' values at the given row ids (e.g.
+  // those of query_compact), in the given order; `rows` of the result is the
+  // input.  An id outside the table throws "Row id out of range: <id>".
+  ResultTable query_rows(const std::vector<std::string> &exprs, const std::vector<int64_t> &rows);
+  // SELECT a, b, ... FROM t [WHERE c] ORDER BY o [ASC|DESC] [LIMIT n] [OFFSET m]
+  // through query_select_ordered's path (one item is allowed; ORDER BY is
+  // required; GROUP BY, DISTINCT, aggregates, window functions and JOIN are
+  // refused).  query_sql_table keeps refusing ORDER BY over several items.
+  ResultTable query_sql_ordered(const std::string &sql);
+  // query_select_ordered as struct<one float32 child per expression, row: int64>.
+  void query_arrow_select_ordered(const std::vector<std::string> &exprs, const std::string &where,
+                                  const std::string &order_by, bool descending, int64_t limit, int64_t offset,
+                                  ArrowArray *out_array, ArrowSchema *out_schema);
+
   const Table &table() const { return table_; }
   const HostTable &host_table() const { return host_table_; }
 

@@ -155,6 +155,56 @@ wx_status wx_prepare_multi(const wx_table *table, const char *const *exprs, int3
  * is out of range or the geometry is invalid. */
 int32_t wx_select_tile_rows(int32_t n_exprs);
 
+/* Row gather with several outputs (late materialisation): n_exprs
+ * expressions (1 .. WX_MAX_OUTPUTS) at a list of row ids.  For k < count,
+ * row = d_rows[k] - row_base (ids of idx_bytes 4 -> int32 or 8 -> int64,
+ * e.g. the row ids of wx_project_filter or wx_topk); d_out_vals[j][k] (each
+ * pointer nullable) = (float)exprs[j] at that row and d_out_rows[k]
+ * (nullable) = out_row_base + row.  Each referenced column is read once per
+ * row.  d_count (device int64, nullable) bounds the count further on the
+ * device (min(count, *d_count)), so the ids of an asynchronous call can be
+ * consumed without a host read.  A row outside [0, n_rows) reads no memory
+ * and every output holds NaN there; nothing is written at k >= count.
+ * Asynchronous unless WX_F_SYNC is set.  n_exprs out of range, a blank
+ * expression, idx_bytes other than 4 / 8 or a negative count return
+ * WX_ERR_INVALID. */
+wx_status wx_gather_multi(const wx_table *table, const char *const *exprs, int32_t n_exprs,
+                          const void *d_rows, int32_t idx_bytes, int64_t row_base, int64_t count,
+                          const int64_t *d_count, const wx_launch *launch, float *const *d_out_vals,
+                          int64_t *d_out_rows, int64_t out_row_base, char *err, size_t errlen);
+/* Build (and cache) the module wx_gather_multi would use, without launching
+ * (works without a GPU, like wx_prepare). */
+wx_status wx_prepare_gather(const wx_table *table, const char *const *exprs, int32_t n_exprs,
+                            const wx_launch *launch, char *err, size_t errlen);
+/* Output positions per workgroup iteration of an n_exprs-output gather (the
+ * diagnostic define list may override the geometry); 0 when n_exprs is out
+ * of range or the geometry is invalid. */
+int32_t wx_gather_tile_rows(int32_t n_exprs);
+
+/* ORDER BY order_expr [DESC] [LIMIT limit] over a multi-column SELECT:
+ * n_exprs expressions (0 .. WX_ORDERED_MAX_EXPRS; 0 = keys and rows only) of
+ * the rows passing cond, in the order of wx_sort_by_key and wx_topk (NaN keys
+ * last in both directions, -0.0 == +0.0, ties by ascending row).  The first
+ * min(limit, passing) positions (limit < 0: all) of d_out_keys (the order
+ * keys), d_out_rows (row_base + row) and d_out_vals[j] are written; every
+ * output pointer is nullable and holds `capacity` entries.  The count goes
+ * to d_count / h_count; a result longer than capacity returns
+ * WX_ERR_CAPACITY with the needed count in *h_count.  The sorted row ids are
+ * computed once, whatever n_exprs: limit <= 32 takes one wx_topk scan and
+ * stays asynchronous (unless h_count is given, or capacity < limit, which
+ * needs a host read of the count); otherwise one ordered compaction of the
+ * key with int32 row ids, a stable pair sort with the row ids as payload
+ * (limited to the head) and the gather, synchronous (scratch: 8 bytes per
+ * table row; at most 2^31 - 1 rows, WX_ERR_UNSUPPORTED beyond).  The
+ * expressions are gathered at the sorted rows in chunks of WX_MAX_OUTPUTS.
+ * $WARPDB_ORDERED_ROUTE=sort forces the second route for small limits. */
+#define WX_ORDERED_MAX_EXPRS 16
+wx_status wx_select_ordered(const wx_table *table, const char *const *exprs, int32_t n_exprs,
+                            const char *cond, const char *order_expr, int32_t descending, int64_t limit,
+                            const wx_launch *launch, int64_t row_base, float *const *d_out_vals,
+                            float *d_out_keys, int64_t *d_out_rows, int64_t capacity, int64_t *d_count,
+                            int64_t *h_count, char *err, size_t errlen);
+
 /* SUM((float)expr) over rows where cond holds, accumulated in double.
  * d_out (device, nullable) receives {sum as double, count as int64 bits};
  * h_sum / h_count (host, nullable) synchronise. */

@@ -70,6 +70,10 @@ EXPORTED_SYMBOLS = (
     "wx_project_filter_multi",
     "wx_prepare_multi",
     "wx_select_tile_rows",
+    "wx_gather_multi",
+    "wx_prepare_gather",
+    "wx_gather_tile_rows",
+    "wx_select_ordered",
     "wx_reduce_sum",
     "wx_reduce_stats",
     "wx_group_sum",
@@ -155,6 +159,10 @@ def load() -> ctypes.CDLL:
         "wx_project_filter_multi": [T, ctypes.POINTER(E), I32, E, L, I32, ctypes.POINTER(P), P, I32, I64, P, pI64, E,
                                     S],
         "wx_prepare_multi": [T, ctypes.POINTER(E), I32, E, L, E, S],
+        "wx_gather_multi": [T, ctypes.POINTER(E), I32, P, I32, I64, I64, P, L, ctypes.POINTER(P), P, I64, E, S],
+        "wx_prepare_gather": [T, ctypes.POINTER(E), I32, L, E, S],
+        "wx_select_ordered": [T, ctypes.POINTER(E), I32, E, E, I32, I64, L, I64, ctypes.POINTER(P), P, P, I64, P, pI64,
+                              E, S],
         "wx_reduce_sum": [T, E, E, L, P, pD, pI64, E, S],
         "wx_reduce_stats": [T, E, E, L, P, ctypes.POINTER(WxStats), E, S],
         "wx_group_sum": [T, E, E, E, L, I32, I64, P, P, P, P, pI64, E, S],
@@ -191,6 +199,8 @@ def load() -> ctypes.CDLL:
     lib.wx_shutdown.restype = None
     lib.wx_select_tile_rows.argtypes = [I32]
     lib.wx_select_tile_rows.restype = ctypes.c_int32
+    lib.wx_gather_tile_rows.argtypes = [I32]
+    lib.wx_gather_tile_rows.restype = ctypes.c_int32
     lib.wx_abi_version.argtypes = []
     lib.wx_abi_version.restype = ctypes.c_int32
     _lib = lib
@@ -303,6 +313,63 @@ def prepare_multi(table: Table, exprs: Sequence[str], cond: Optional[str] = None
 def select_tile_rows(n_exprs: int) -> int:
     """Rows per compaction tile of an n_exprs-output call (0: out of range)."""
     return int(load().wx_select_tile_rows(n_exprs))
+
+
+def gather_multi(table: Table, exprs: Sequence[str], d_rows: int, idx_bytes: int, count: int, launch: WxLaunch,
+                 d_out_vals: Sequence[int], d_out_rows: int = 0, row_base: int = 0, out_row_base: int = 0,
+                 d_count: int = 0) -> None:
+    """len(exprs) expressions at `count` row ids (d_rows, int32 or int64 by
+    idx_bytes; row = id - row_base): d_out_vals[j] (0 = not wanted) receives
+    expression j, d_out_rows out_row_base + row.  d_count (device int64)
+    bounds the count on the device.  A shorter d_out_vals is padded with
+    nulls."""
+    lib = load()
+    err = _err()
+    outs = list(d_out_vals) + [0] * (len(exprs) - len(d_out_vals))
+    ptrs = (ctypes.c_void_p * max(1, len(outs)))(*[p or None for p in outs])
+    _check(lib.wx_gather_multi(ctypes.byref(table.c), _expr_array(exprs), len(exprs), d_rows or None, idx_bytes,
+                               row_base, count, d_count or None, ctypes.byref(launch), ptrs, d_out_rows or None,
+                               out_row_base, err, len(err)), err)
+
+
+def prepare_gather(table: Table, exprs: Sequence[str], launch: Optional[WxLaunch] = None) -> None:
+    """Compile the module gather_multi would use (no GPU needed)."""
+    lib = load()
+    err = _err()
+    L = launch or make_launch()
+    _check(lib.wx_prepare_gather(ctypes.byref(table.c), _expr_array(exprs), len(exprs), ctypes.byref(L), err,
+                                 len(err)), err)
+
+
+def gather_tile_rows(n_exprs: int) -> int:
+    """Output positions per workgroup iteration of an n_exprs-output gather (0: out of range)."""
+    return int(load().wx_gather_tile_rows(n_exprs))
+
+
+def select_ordered(table: Table, exprs: Sequence[str], cond: Optional[str], order_expr: Optional[str],
+                   descending: bool, limit: int, launch: WxLaunch, d_out_vals: Sequence[int], d_out_keys: int = 0,
+                   d_out_rows: int = 0, capacity: int = 0, row_base: int = 0, d_count: int = 0,
+                   want_count: bool = True) -> Optional[int]:
+    """ORDER BY order_expr [DESC] [LIMIT limit] (limit < 0: all) over
+    len(exprs) expressions (0 .. 16) of the rows passing cond: the first
+    min(limit, passing) keys, global rows and values, `capacity` entries per
+    output (0 = not wanted).  On WX_ERR_CAPACITY the raised error carries the
+    needed count in `.count`."""
+    lib = load()
+    err = _err()
+    h = ctypes.c_int64(-1)
+    outs = list(d_out_vals) + [0] * (len(exprs) - len(d_out_vals))
+    ptrs = (ctypes.c_void_p * max(1, len(outs)))(*[p or None for p in outs])
+    st = lib.wx_select_ordered(ctypes.byref(table.c), _expr_array(exprs), len(exprs), _enc(cond), _enc(order_expr),
+                               1 if descending else 0, limit, ctypes.byref(launch), row_base, ptrs,
+                               d_out_keys or None, d_out_rows or None, capacity, d_count or None,
+                               ctypes.byref(h) if want_count else None, err, len(err))
+    try:
+        _check(st, err)
+    except WarpExecError as e:
+        e.count = h.value
+        raise
+    return h.value if want_count else None
 
 
 def reduce_sum(table: Table, expr: str, cond: Optional[str], launch: WxLaunch, d_out: int = 0,

@@ -203,6 +203,60 @@ PYBIND11_MODULE(pywarpdb, m) {
           },
           py::arg("exprs"), py::arg("where") = "",
           "query_select as struct<one float32 child per expression, row: int64> (Arrow C Data Interface capsules).")
+      .def(
+          "query_select_ordered",
+          [](WarpDB &db, const std::vector<std::string> &exprs, const std::string &where, const std::string &order_by,
+             bool descending, int64_t limit, int64_t offset) {
+            warpdb::ResultTable t;
+            {
+              py::gil_scoped_release nogil;
+              t = db.query_select_ordered(exprs, where, order_by, descending, limit, offset);
+            }
+            return table_arrays(t);
+          },
+          py::arg("exprs"), py::arg("where"), py::arg("order_by"), py::arg("descending") = false,
+          py::arg("limit") = -1, py::arg("offset") = 0,
+          "Several expressions of the rows WHERE keeps, ordered by one key expression (one sort or top-K scan, "
+          "then a fused row gather) -> (names, [float32 arrays], int64 rows).")
+      .def(
+          "query_rows",
+          [](WarpDB &db, const std::vector<std::string> &exprs, const std::vector<int64_t> &rows) {
+            warpdb::ResultTable t;
+            {
+              py::gil_scoped_release nogil;
+              t = db.query_rows(exprs, rows);
+            }
+            return table_arrays(t);
+          },
+          py::arg("exprs"), py::arg("rows"),
+          "Several expressions at the given row ids (late materialisation) -> (names, [float32 arrays], int64 rows).")
+      .def(
+          "query_sql_ordered",
+          [](WarpDB &db, const std::string &sql) {
+            warpdb::ResultTable t;
+            {
+              py::gil_scoped_release nogil;
+              t = db.query_sql_ordered(sql);
+            }
+            return table_arrays(t);
+          },
+          py::arg("sql"),
+          "SELECT a, b, ... FROM t [WHERE c] ORDER BY o [ASC|DESC] [LIMIT n] [OFFSET m] -> "
+          "(names, [float32 arrays], int64 rows).")
+      .def(
+          "query_arrow_select_ordered",
+          [](WarpDB &db, const std::vector<std::string> &exprs, const std::string &where, const std::string &order_by,
+             bool descending, int64_t limit, int64_t offset) {
+            return export_with<ArrowArray>(
+                [&](ArrowArray *a, ArrowSchema *s) {
+                  db.query_arrow_select_ordered(exprs, where, order_by, descending, limit, offset, a, s);
+                },
+                arrow_capsules);
+          },
+          py::arg("exprs"), py::arg("where"), py::arg("order_by"), py::arg("descending") = false,
+          py::arg("limit") = -1, py::arg("offset") = 0,
+          "query_select_ordered as struct<one float32 child per expression, row: int64> (Arrow C Data Interface "
+          "capsules).")
       .def("query_sum", &WarpDB::query_sum, py::call_guard<py::gil_scoped_release>())
       .def("query_multi_gpu_sum", &WarpDB::query_multi_gpu_sum, py::call_guard<py::gil_scoped_release>())
       .def(

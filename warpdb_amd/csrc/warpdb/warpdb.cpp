@@ -811,6 +811,200 @@ void WarpDB::query_arrow_select(const std::vector<std::string> &exprs, const std
   export_select_to_arrow(r.names, columns, r.rows.data(), static_cast<int64_t>(r.rows.size()), out_array, out_schema);
 }
 
+// ------------------------------------- ordered multi-column results, row gather
+namespace {
+// Parse, validate and lower a list of plain expressions as query_select
+// does; `who` names the entry point in the messages.
+void lower_select_list(const std::vector<std::string> &exprs, const std::unordered_set<std::string> &cols,
+                       const char *who, std::vector<std::string> &lowered, std::vector<std::string> &names) {
+  if (exprs.empty()) throw std::runtime_error("Empty SELECT list");
+  if (exprs.size() > WarpDB::kMaxSelectExprs)
+    throw std::runtime_error(std::string(who) + " takes at most " + std::to_string(WarpDB::kMaxSelectExprs) +
+                             " expressions");
+  for (size_t i = 0; i < exprs.size(); ++i) {
+    if (blank(exprs[i])) throw std::runtime_error("Empty query expression");
+    ASTNodePtr ex;
+    try {
+      ex = parse_expression(tokenize(exprs[i]));
+    } catch (const std::exception &err) {
+      throw std::runtime_error(std::string("Failed to parse expression: ") + err.what());
+    }
+    validate_ast(ex.get(), cols);
+    if (dynamic_cast<const AggregationNode *>(ex.get()))
+      throw std::runtime_error(std::string(who) + " takes plain expressions, not aggregates");
+    lowered.push_back(ex->to_cuda_expr());
+    names.push_back(column_name(ex.get(), i));
+  }
+}
+
+std::vector<int64_t> download_rows(const void *d, int64_t n, int device) {
+  std::vector<int64_t> h(static_cast<size_t>(n), 0);
+  DevGuard g(device);
+  if (n) hip_ok(hipMemcpy(h.data(), d, sizeof(int64_t) * static_cast<size_t>(n), hipMemcpyDeviceToHost), "hipMemcpy");
+  return h;
+}
+
+// The lowered expressions of the rows `cond` keeps, ordered by order_c:
+// positions [offset, offset + limit) of the ordered result (limit < 0: to
+// the end).  One wx_select_ordered call; only offset + limit rows are
+// computed and downloaded.
+void ordered_run(const Table &table, const std::vector<std::string> &exprs_c, const std::string &cond_c,
+                 const std::string &order_c, bool descending, int64_t limit, int64_t offset,
+                 warpdb::ResultTable &out) {
+  const int64_t n = table.num_rows;
+  offset = std::max<int64_t>(0, offset);
+  const int64_t want = limit < 0 ? -1 : (limit > INT64_MAX - offset ? INT64_MAX : offset + limit);
+  const int64_t cap = want < 0 ? n : std::min(n, want);
+  const size_t m = exprs_c.size();
+  std::vector<std::unique_ptr<DeviceBuffer>> vals;
+  std::vector<const char *> ex;
+  std::vector<float *> dst;
+  for (size_t j = 0; j < m; ++j) {
+    vals.push_back(std::make_unique<DeviceBuffer>(table.device, sizeof(float) * static_cast<size_t>(cap ? cap : 1)));
+    ex.push_back(exprs_c[j].c_str());
+    dst.push_back(static_cast<float *>(vals[j]->ptr));
+  }
+  DeviceBuffer rows(table.device, sizeof(int64_t) * static_cast<size_t>(cap ? cap : 1));
+  WxTableView v(table);
+  wx_launch L = sync_launch(table.device);
+  char err[8192];
+  int64_t count = 0;
+  throw_on(wx_select_ordered(&v.table, ex.data(), static_cast<int32_t>(m), cond_c.c_str(), order_c.c_str(),
+                             descending ? 1 : 0, want, &L, 0, dst.data(), nullptr, static_cast<int64_t *>(rows.ptr),
+                             cap, nullptr, &count, err, sizeof(err)),
+           err);
+  const int64_t first = std::min(offset, count), keep = count - first;
+  out.columns.clear();
+  for (size_t j = 0; j < m; ++j) out.columns.push_back(download(dst[j] + first, keep, table.device));
+  out.rows = download_rows(static_cast<int64_t *>(rows.ptr) + first, keep, table.device);
+}
+}  // namespace
+
+WarpDB::ResultTable WarpDB::query_select_ordered(const std::vector<std::string> &exprs, const std::string &where,
+                                                 const std::string &order_by, bool descending, int64_t limit,
+                                                 int64_t offset) {
+  const auto cols = names_of(table_);
+  ResultTable out;
+  std::vector<std::string> lowered;
+  lower_select_list(exprs, cols, "query_select_ordered", lowered, out.names);
+  std::string cond_c, order_c;
+  if (!blank(where)) {
+    try {
+      auto cx = parse_expression(tokenize(where));
+      validate_ast(cx.get(), cols);
+      cond_c = cx->to_cuda_expr();
+    } catch (const std::exception &err) {
+      throw std::runtime_error(std::string("Failed to parse WHERE clause: ") + err.what());
+    }
+  }
+  if (blank(order_by)) throw std::runtime_error("Empty ORDER BY expression");
+  try {
+    auto ox = parse_expression(tokenize(order_by));
+    validate_ast(ox.get(), cols);
+    if (dynamic_cast<const AggregationNode *>(ox.get())) throw std::runtime_error("aggregates are not supported here");
+    order_c = ox->to_cuda_expr();
+  } catch (const std::exception &err) {
+    throw std::runtime_error(std::string("Failed to parse ORDER BY expression: ") + err.what());
+  }
+  ordered_run(table_, lowered, cond_c, order_c, descending, limit, offset, out);
+  return out;
+}
+
+WarpDB::ResultTable WarpDB::query_rows(const std::vector<std::string> &exprs, const std::vector<int64_t> &rows) {
+  ResultTable out;
+  std::vector<std::string> lowered;
+  lower_select_list(exprs, names_of(table_), "query_rows", lowered, out.names);
+  for (int64_t r : rows)
+    if (r < 0 || r >= table_.num_rows) throw std::runtime_error("Row id out of range: " + std::to_string(r));
+  const int64_t count = static_cast<int64_t>(rows.size());
+  const size_t m = lowered.size();
+  const size_t width = std::min<size_t>(m, WX_MAX_OUTPUTS);
+  DeviceBuffer ids(table_.device, sizeof(int64_t) * static_cast<size_t>(count ? count : 1));
+  {
+    DevGuard g(table_.device);
+    if (count)
+      hip_ok(hipMemcpy(ids.ptr, rows.data(), sizeof(int64_t) * static_cast<size_t>(count), hipMemcpyHostToDevice),
+             "hipMemcpy");
+  }
+  std::vector<std::unique_ptr<DeviceBuffer>> vals;
+  for (size_t j = 0; j < width; ++j)
+    vals.push_back(std::make_unique<DeviceBuffer>(table_.device, sizeof(float) * static_cast<size_t>(count ? count : 1)));
+  WxTableView v(table_);
+  wx_launch L = sync_launch(table_.device);
+  char err[8192];
+  for (size_t first = 0; first < m; first += WX_MAX_OUTPUTS) {
+    const size_t k = std::min<size_t>(WX_MAX_OUTPUTS, m - first);
+    const char *ex[WX_MAX_OUTPUTS] = {nullptr, nullptr, nullptr, nullptr};
+    float *dst[WX_MAX_OUTPUTS] = {nullptr, nullptr, nullptr, nullptr};
+    for (size_t j = 0; j < k; ++j) {
+      ex[j] = lowered[first + j].c_str();
+      dst[j] = static_cast<float *>(vals[j]->ptr);
+    }
+    throw_on(wx_gather_multi(&v.table, ex, static_cast<int32_t>(k), ids.ptr, 8, 0, count, nullptr, &L, dst, nullptr, 0,
+                             err, sizeof(err)),
+             err);
+    for (size_t j = 0; j < k; ++j) out.columns.push_back(download(vals[j]->ptr, count, table_.device));
+  }
+  out.rows = rows;
+  return out;
+}
+
+WarpDB::ResultTable WarpDB::query_sql_ordered(const std::string &sql) {
+  QueryAST ast;
+  try {
+    ast = parse_query(tokenize(sql));
+  } catch (const std::exception &e) {
+    throw std::runtime_error(std::string("Failed to parse SQL: ") + e.what());
+  }
+  const auto cols = names_of(table_);
+  auto validate_ctx = [&](const ASTNode *n, const std::string &ctx) {
+    try {
+      validate_ast(n, cols);
+    } catch (const std::exception &e) {
+      throw std::runtime_error(ctx + ": " + e.what());
+    }
+  };
+  if (ast.select_list.empty()) throw std::runtime_error("Empty SELECT list");
+  if (!ast.joins.empty()) throw std::runtime_error("JOIN is not supported by query_sql_ordered");
+  if (ast.group_by) throw std::runtime_error("GROUP BY is not supported by query_sql_ordered (use query_sql_table)");
+  if (ast.distinct) throw std::runtime_error("DISTINCT is not supported by query_sql_ordered");
+  for (const auto &e : ast.select_list) {
+    if (dynamic_cast<const WindowFunctionNode *>(e.get()))
+      throw std::runtime_error("window functions are not supported by query_sql_ordered");
+    if (dynamic_cast<const AggregationNode *>(e.get()))
+      throw std::runtime_error("aggregates are not supported by query_sql_ordered (plain expressions only)");
+  }
+  if (!ast.order_by) throw std::runtime_error("query_sql_ordered needs an ORDER BY clause");
+  if (dynamic_cast<const AggregationNode *>(ast.order_by->expr.get()))
+    throw std::runtime_error("aggregates are not supported by query_sql_ordered (plain expressions only)");
+  for (const auto &e : ast.select_list) validate_ctx(e.get(), "SELECT clause");
+  if (ast.where) validate_ctx(ast.where->get(), "WHERE clause");
+  validate_ctx(ast.order_by->expr.get(), "ORDER BY");
+  const size_t m = ast.select_list.size();
+  if (m > kMaxSelectExprs)
+    throw std::runtime_error("a select list takes at most " + std::to_string(kMaxSelectExprs) + " expressions");
+  ResultTable out;
+  std::vector<std::string> lowered;
+  for (size_t i = 0; i < m; ++i) {
+    out.names.push_back(column_name(ast.select_list[i].get(), i));
+    lowered.push_back(ast.select_list[i]->to_cuda_expr());
+  }
+  const std::string cond = ast.where ? (*ast.where)->to_cuda_expr() : std::string();
+  const int64_t off = ast.offset ? std::max(0, ast.offset->count) : 0;
+  const int64_t lim = ast.limit ? std::max(0, ast.limit->count) : -1;
+  ordered_run(table_, lowered, cond, ast.order_by->expr->to_cuda_expr(), !ast.order_by->ascending, lim, off, out);
+  return out;
+}
+
+void WarpDB::query_arrow_select_ordered(const std::vector<std::string> &exprs, const std::string &where,
+                                        const std::string &order_by, bool descending, int64_t limit, int64_t offset,
+                                        ArrowArray *out_array, ArrowSchema *out_schema) {
+  const ResultTable r = query_select_ordered(exprs, where, order_by, descending, limit, offset);
+  std::vector<const float *> columns;
+  for (const auto &c : r.columns) columns.push_back(c.data());
+  export_select_to_arrow(r.names, columns, r.rows.data(), static_cast<int64_t>(r.rows.size()), out_array, out_schema);
+}
+
 WarpDB::ResultTable WarpDB::query_sql_table(const std::string &sql) {
   QueryAST ast;
   try {
