@@ -2,7 +2,9 @@
 // UndefinedBehaviorSanitizer (no GPU): the expression / SQL front end on
 // random token soup and pathological nesting, and the parallel CSV parser
 // (csv_parse.cpp) against a sequential std::getline + strto* reading of the
-// same text, including blanks, '+', hex, CRLF, blank lines, missing cells.
+// same text, including blanks, '+', hex, CRLF, blank lines, missing cells;
+// and warpexec's code generator (codegen.cpp), which parses expression text
+// and define lists that come from outside.
 // Built by `make -C tests/cpp sanitize_test` with -fsanitize=address,undefined.
 #include <cmath>
 #include <cstdio>
@@ -16,6 +18,7 @@
 
 #include "warpdb/expression.hpp"
 #include "../../warpdb_amd/csrc/warpdb/internal.hpp"
+#include "../../warpdb_amd/csrc/warpexec/wx_host.hpp"
 
 static int failures = 0;
 #define CHECK(c)                                                   \
@@ -171,9 +174,70 @@ static void fuzz_csv() {
   CHECK(t.num_rows() == 0);
 }
 
+static std::vector<std::string> identifiers(const char *s) {
+  std::vector<std::string> ids;
+  wx::scan_identifiers(s, ids);
+  return ids;
+}
+
+static bool rejects(const wx_table &t, const char *expr, wx_status st) {
+  try {
+    (void)wx::used_columns(&t, {expr});
+  } catch (const wx::WxError &e) {
+    return e.st == st;
+  }
+  return false;
+}
+
+// warpexec's code generator on the edges of its text parsing (no HIP call:
+// codegen.cpp is compiled into this program as it is into libwarpexec.so)
+static void codegen_text() {
+  using V = std::vector<std::string>;
+  CHECK(identifiers(nullptr).empty() && identifiers("").empty() && identifiers(" \t(+)").empty());
+  CHECK(identifiers("price") == V{"price"});                     // an identifier ends the string
+  CHECK(identifiers("f (x) + g\t(y[idx]) + h ") == (V{"x", "y", "idx", "h"}));  // blanks before '(': a call
+  CHECK(identifiers("1e5f + 10.0f*a_1 - .5 + 0x1F + 7") == V{"a_1"});  // literals and their suffixes
+  CHECK(identifiers("_x1e5(") .empty() && identifiers("9") .empty());
+
+  float cell = 0;
+  const wx_col cols[] = {{"price", WX_FLOAT32, &cell}, {nullptr, WX_FLOAT32, &cell}, {"note", WX_STRING, &cell},
+                         {"qty", WX_INT64, nullptr}};
+  const wx_table t{1, 4, cols}, none{0, 0, nullptr};
+  CHECK(wx::used_columns(&none, {}).empty() && wx::used_columns(&none, {nullptr, "", "price[idx]"}).empty());
+  const auto used = wx::used_columns(&t, {"price(1) + price[idx]", nullptr, "note(2)"});
+  CHECK(used.size() == 1 && used[0].name == "price" && std::string(used[0].ctype) == "float" &&
+        used[0].table_index == 0);
+  CHECK(rejects(t, "note[idx]", WX_ERR_UNSUPPORTED));  // a string column
+  CHECK(rejects(t, "qty[idx]", WX_ERR_INVALID));       // no device pointer
+  std::vector<std::string> names;
+  std::vector<wx_col> many;
+  std::string all;
+  for (int i = 0; i < WX_MAX_COLS + 1; ++i) names.push_back("c" + std::to_string(i));
+  for (auto &n : names) {
+    many.push_back({n.c_str(), WX_INT32, &cell});
+    all += n + "[idx] ";
+  }
+  CHECK(rejects(wx_table{1, (int32_t)many.size(), many.data()}, all.c_str(), WX_ERR_UNSUPPORTED));
+
+  CHECK(wx::define_value("", "A", 7) == 7 && wx::define_value("A", "A", 7) == 7 && wx::define_value("AB=5", "A", 7) == 7);
+  CHECK(wx::define_value("A=", "A", 7) == 0 && wx::define_value("A=x", "A", 7) == 0 && wx::define_value("=3", "", 7) == 3);
+  CHECK(wx::define_value(",,A=3,,", "A", 7) == 3 && wx::define_value("A=3,B,A=4,", "A", 7) == 4);
+
+  wx::Spec spec;
+  spec.op = WX_OP_UTIL;
+  spec.extra = ",,A=1,,B,=3,C=,";  // empty items, an empty name, an empty value
+  const std::string src = spec.source();
+  CHECK(src.find("#define A 1\n#define B 1\n#define  3\n#define C \n") != std::string::npos);
+  CHECK(src.find("#define WX_DIAG 1") == std::string::npos && src.find("wx_util.hip") != std::string::npos);
+  spec.extra = "WX_GP_DIAG";
+  CHECK(spec.source().find("#define WX_DIAG 1\n#define WX_GP_DIAG 1\n") != std::string::npos);
+  CHECK(spec.key_string().find("|x=WX_GP_DIAG|") != std::string::npos);
+}
+
 int main() {
   fuzz_front_end();
   fuzz_csv();
+  codegen_text();
   if (failures) return 1;
   std::printf("sanitize_test: all passed\n");
   return 0;

@@ -851,7 +851,7 @@ def test_concurrent_streams_from_threads():
     """Four host threads, one HIP stream each, interleave compaction, SUM, top-K
     and radix sorts on their own tables; every result equals the serial one.
     The runtime keeps one workspace per (device, stream) and locks only its
-    shared maps (warpexec.cpp `workspace`), so this must not race."""
+    shared maps (runtime.cpp `workspace`), so this must not race."""
     import threading
 
     n_threads, iters = 4, 6
@@ -924,7 +924,7 @@ def test_workspace_growth_on_fresh_stream_under_load():
     words, tickets, radix status) while three other streams keep the GPU busy
     and the null stream is held by a spin kernel.  The zero-fills of fresh
     workspace buffers must be ordered before the first kernel that reads them
-    (warpexec.cpp `ensure`: hipMemsetAsync on the workspace stream; the
+    (runtime.cpp `ensure`: hipMemsetAsync on the workspace stream; the
     round-5 abort came from null-stream fills)."""
     import threading
 

@@ -5,2868 +5,12 @@
 // built once per (device arch, query shape) with hiprtc for gfx950, cached in
 // memory and on disk, and launched on the caller's stream into per-(device,
 // stream) workspaces.  Kernels: warpdb_amd/csrc/kernels/wx_*.hip (one source per family).
-#include "warpexec.h"
-
-#include <hip/hip_runtime.h>
-#include <hip/hiprtc.h>
-
-#include <dlfcn.h>
-#include <sys/stat.h>
-#include <unistd.h>
-
-#include <algorithm>
-#include <atomic>
-#include <cctype>
-#include <cstdarg>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <fstream>
-#include <map>
-#include <memory>
-#include <mutex>
-#include <sstream>
-#include <stdexcept>
-#include <string>
-#include <thread>
-#include <unordered_map>
-#include <vector>
-
-#include "../kernels/wx_args.h"
-#include "../kernels/wx_select_args.h"
-#include "../kernels/wx_gather_args.h"
-#include "wx_embedded.inc"  // kWxArgsSrc, kWxSources (the kernel sources; generated by the Makefile)
-
-namespace {
-
-struct WxError {
-  wx_status st;
-  std::string msg;
-};
-
-[[noreturn]] void fail(wx_status st, const std::string &m) { throw WxError{st, m}; }
-
-#define WX_HIP(call)                                                                          \
-  do {                                                                                        \
-    hipError_t e_ = (call);                                                                   \
-    if (e_ != hipSuccess) fail(WX_ERR_DEVICE, std::string("HIP error: ") + #call + ": " +     \
-                                                  hipGetErrorString(e_));                     \
-  } while (0)
-
-// g_mu guards the shared maps (devices and their modules, workspaces) and
-// the timing-event pool; it is never held across a compile or a device
-// synchronisation, so host threads driving different devices
-// (multi_gpu.cpp) run concurrently.
-std::recursive_mutex g_mu;
-using Lock = std::lock_guard<std::recursive_mutex>;
-std::atomic<int64_t> g_compiles{0}, g_hits{0};
-
-// ------------------------------------------------------------------ modules
-struct Module {
-  hipModule_t mod = nullptr;
-  std::mutex mu;
-  std::unordered_map<std::string, hipFunction_t> fns;
-  hipFunction_t fn(const char *name) {
-    std::lock_guard<std::mutex> lk(mu);
-    auto it = fns.find(name);
-    if (it != fns.end()) return it->second;
-    hipFunction_t f;
-    WX_HIP(hipModuleGetFunction(&f, mod, name));
-    fns.emplace(name, f);
-    return f;
-  }
-};
-
-// One workspace per (device, stream): look-back tile status, counters,
-// reduction partials, group tables, top-K candidates, sort scratch.
-struct Buf {
-  void *p = nullptr;
-  size_t bytes = 0;
-};
-
-struct Workspace {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  // Held for a whole operation (enqueue, internal syncs, host reads): two
-  // host threads on one (device, stream) -- e.g. pywarpdb calls with the GIL
-  // released, all on the null stream -- take turns instead of interleaving
-  // epochs, memsets and buffer growth.
-  std::recursive_mutex op_mu;
-  Buf ctrs;        // u64[8]: [0] ticket, [1] error bits, [2] retired workgroups (compaction)
-  Buf status;      // u64[n_tiles + 1] compaction look-back words {epoch | flag | value}
-  uint32_t cs_epoch = 0;  // epoch of the last compaction launch (0: words all zero)
-  uint64_t host_word = 0;  // landing slot of small synchronous D2H reads (outlives the copy)
-  uint64_t *h_err = nullptr;  // pinned: the error words of ctrs / g_ctrs, read with one stream sync
-  bool topk_clean = false;    // topk_thresh is zero (see do_topk)
-  Buf part_sum, part_cnt, part_min, part_max;
-  Buf sum_out;     // 24 bytes (wx_stats)
-  Buf count_tmp;   // i64 scratch for host-count requests
-  // group state (kept clean between calls by wx_group_finalize)
-  Buf g_win_sum, g_win_cnt, g_tag, g_sum, g_cnt, g_used, g_ctrs, g_ngroups;
-  uint32_t g_hcap = 0;
-  // MIN / MAX group state: ~0 / 0 when unused (restored by wx_group_finalize)
-  Buf g_win_min, g_win_max, g_min, g_max;
-  uint32_t g_mm_cap = 0;
-  Buf g_sorted;  // large GROUP BY: sorted general-key entries
-  // many-key list merge (wx_group_merge_lists): merged groups, head flags,
-  // per-span head counts, totals
-  Buf gl_keys, gl_sums, gl_cnts, gl_head, gl_blk, gl_meta;
-  // range-partitioned GROUP BY (many keys): per-workgroup range words,
-  // per-(workgroup, partition) rows, the run directory, the tiles' sorted
-  // values and bins, work items and their partial windows, the range
-  // summary, per-partition key counts; nothing needs zeroing between calls
-  Buf gp_order, gp_mm, gp_pcount, gp_ptotal, gp_dir, gp_vals, gp_bins, gp_work, gp_nwork, gp_pitem, gp_psum, gp_pcnt, gp_summary, gp_pnz;
-  struct GpMemo {
-    int64_t lo = 0, hi = -1;
-    bool window = false;  // the range fit the LDS window (taken without a read-back)
-    int uses = 0;
-  };
-  std::unordered_map<uint64_t, GpMemo> gp_memo;  // last key range per (expressions, columns, rows)
-  Buf cand_k, cand_i, topk_thresh;
-  // ORDER BY .. LIMIT heads of any length: keys, SELECT values, local rows,
-  // positions and the passing count of one shard; the merge's candidates
-  Buf hd_keys, hd_vals, hd_rows, hd_idx, hd_count, hm_keys, hm_idx, hm_count;
-  Buf so_keys, so_rows, so_cnt;  // ordered multi-column SELECT, top-K route: keys, global rows, count
-  Buf sort_keys, sort_copy_a, sort_copy_v;
-  Buf ro_vals, ro_keys;  // row-order GROUP BY: passing values and keys, sorted by key
-  // the general row-order fold: group starts, chunk prefixes, the big groups' count + list
-  Buf gf_starts, gf_chunks, gf_big;
-  // radix sort: histograms + digit bases, look-back words, per-pass
-  // ticket / abort words, ping-pong buffers
-  Buf rs_hist, rs_status, rs_ctl, rs_tmp_k, rs_tmp_v;
-  uint32_t rs_epoch = 0;
-  // row-order GROUP BY over a key span <= 2048 (wx_group_rows.hip):
-  // per-range bin counts, per-range output offsets, bin totals and bases
-  Buf ro_cnt, ro_off, ro_tot;
-  Buf ro_info;  // the direct span path: groups, passing rows, outside flag, min / max key
-  // the direct span path's recent misses (a key outside the guessed span):
-  // calls left before it is tried again for the same expressions / table
-  std::unordered_map<uint64_t, int> ro_miss;
-  // row-order folds of big groups (wx_xf_big_*): entries, chunk sums, chunk records
-  Buf xf_ent, xf_approx, xf_rec;
-  std::vector<int64_t> xf_host;  // the entries' host copy (outlives its asynchronous upload)
-  Buf diag;  // WX_DIAG_TIMELINE per-workgroup times
-  std::vector<Buf *> bufs;  // every buffer ensure() has allocated: wx_shutdown frees them all
-};
-
-struct DeviceState {
-  std::string arch;
-  int cus = 256;
-  std::unordered_map<std::string, std::shared_ptr<Module>> modules;  // key: query spec
-};
-
-std::map<int, DeviceState> g_devices;
-std::map<std::pair<int, hipStream_t>, std::unique_ptr<Workspace>> g_ws;
-
-struct TimedLaunch {
-  hipEvent_t a, b;
-  int device;
-};
-// the WX_F_TIME launches of the process not yet read (any thread: the C++
-// multi-GPU path launches from one host thread per device), under g_mu
-std::vector<TimedLaunch> g_timed;
-std::map<int, std::vector<hipEvent_t>> g_event_pool;  // per device
-
-// Grow a workspace buffer.  Every fill of a workspace buffer is ordered on
-// the workspace's own stream: the kernels that rely on zeroed look-back words
-// and tickets run there, and torch's pool streams are non-blocking, so a
-// null-stream hipMemset is not ordered before them (hipMemset returns before
-// the fill lands: tools/memset_order_probe.hip).  hipFree
-// synchronises the device, so no in-flight kernel still uses the old buffer.
-void ensure(Workspace &w, Buf &b, size_t bytes, bool zero) {
-  if (b.bytes >= bytes && b.p) return;
-  if (b.p) WX_HIP(hipFree(b.p));
-  b.p = nullptr;
-  b.bytes = 0;
-  size_t want = std::max<size_t>(bytes, 256);
-  WX_HIP(hipMalloc(&b.p, want));
-  if (std::find(w.bufs.begin(), w.bufs.end(), &b) == w.bufs.end()) w.bufs.push_back(&b);
-  if (zero) WX_HIP(hipMemsetAsync(b.p, 0, want, w.stream));
-  b.bytes = want;
-}
-
-class DevGuard {
- public:
-  explicit DevGuard(int dev) {
-    if (hipGetDevice(&prev_) != hipSuccess) prev_ = -1;
-    if (prev_ != dev) WX_HIP(hipSetDevice(dev));
-    dev_ = dev;
-  }
-  ~DevGuard() {
-    if (prev_ >= 0 && prev_ != dev_) (void)hipSetDevice(prev_);
-  }
-
- private:
-  int prev_ = -1, dev_ = 0;
-};
-
-std::string env_or(const char *k, const char *dflt) {
-  const char *v = std::getenv(k);
-  return (v && *v) ? std::string(v) : std::string(dflt);
-}
-
-DeviceState &device_state(int dev, bool need_device) {
-  Lock lk(g_mu);
-  auto it = g_devices.find(dev);
-  if (it != g_devices.end() && (!need_device || !it->second.arch.empty())) return it->second;
-  DeviceState &d = g_devices[dev];
-  if (need_device) {
-    hipDeviceProp_t prop;
-    WX_HIP(hipGetDeviceProperties(&prop, dev));
-    d.arch = prop.gcnArchName;
-    d.cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-  }
-  return d;
-}
-
-Workspace &workspace(int dev, hipStream_t s) {
-  Lock lk(g_mu);
-  auto key = std::make_pair(dev, s);
-  auto it = g_ws.find(key);
-  if (it != g_ws.end()) return *it->second;
-  auto w = std::make_unique<Workspace>();
-  w->device = dev;
-  w->stream = s;
-  ensure(*w, w->ctrs, 64, true);
-  Workspace &ref = *w;
-  g_ws.emplace(key, std::move(w));
-  return ref;
-}
-
-using OpLock = std::lock_guard<std::recursive_mutex>;
-
-// --------------------------------------------------------------- codegen
-struct UsedCol {
-  std::string name;
-  const char *ctype;
-  int table_index;
-};
-
-const char *ctype_of(int32_t dt) {
-  switch (dt) {  // src/jit.cpp:31-45
-    case WX_INT32: return "int";
-    case WX_INT64: return "long long";
-    case WX_FLOAT32: return "float";
-    case WX_FLOAT64: return "double";
-    default: return nullptr;
-  }
-}
-
-
-// Identifiers that occur in the lowered C expression text.
-void scan_identifiers(const char *s, std::vector<std::string> &out) {
-  if (!s) return;
-  for (size_t i = 0; s[i];) {
-    unsigned char c = (unsigned char)s[i];
-    if (std::isalpha(c) || c == '_') {
-      size_t j = i;
-      while (s[j] && (std::isalnum((unsigned char)s[j]) || s[j] == '_')) ++j;
-      size_t k = j;
-      while (s[k] == ' ' || s[k] == '\t') ++k;
-      if (s[k] != '(') out.emplace_back(s + i, j - i);  // f(...) names a function, not a column
-      i = j;
-    } else if (std::isdigit(c)) {  // numeric literal incl. suffixes (10.0f, 1e5)
-      size_t j = i;
-      while (s[j] && (std::isalnum((unsigned char)s[j]) || s[j] == '.' || s[j] == '_')) ++j;
-      i = j;
-    } else {
-      ++i;
-    }
-  }
-}
-
-std::vector<UsedCol> used_columns(const wx_table *t, const std::vector<const char *> &exprs);
-std::vector<UsedCol> used_columns(const wx_table *t, std::initializer_list<const char *> exprs) {
-  return used_columns(t, std::vector<const char *>(exprs));
-}
-std::vector<UsedCol> used_columns(const wx_table *t, const std::vector<const char *> &exprs) {
-  std::vector<std::string> ids;
-  for (const char *e : exprs) scan_identifiers(e, ids);
-  std::vector<UsedCol> used;
-  for (int32_t c = 0; c < t->n_cols; ++c) {
-    const char *nm = t->cols[c].name;
-    if (!nm) continue;
-    if (std::find(ids.begin(), ids.end(), std::string(nm)) == ids.end()) continue;
-    const char *ct = ctype_of(t->cols[c].dtype);
-    if (!ct)
-      fail(WX_ERR_UNSUPPORTED, std::string("column ") + nm + " has a type the engine cannot evaluate (string)");
-    if (!t->cols[c].d_ptr && t->n_rows > 0) fail(WX_ERR_INVALID, std::string("column ") + nm + " has no device pointer");
-    used.push_back({nm, ct, c});
-  }
-  if (used.size() > WX_MAX_COLS) fail(WX_ERR_UNSUPPORTED, "more than 16 columns referenced by one query");
-  return used;
-}
-
-bool blank(const char *s) {
-  if (!s) return true;
-  for (; *s; ++s)
-    if (!std::isspace((unsigned char)*s)) return false;
-  return true;
-}
-
-std::string one_line(const char *s) {
-  std::string r = s ? s : "";
-  for (char &c : r)
-    if (c == '\n' || c == '\r') c = ' ';
-  return r;
-}
-
-std::string read_custom(const wx_launch *L) {
-  if (L && (L->flags & WX_F_NO_CUSTOM)) return std::string();
-  if (L && L->custom_src) return std::string(L->custom_src);
-  // src/jit.cpp:65-73 reads ./custom.cu on every call; so do we (a changed
-  // file yields a different cache key).
-  std::string path = env_or("WARPDB_CUSTOM_PATH", "custom.cu");
-  std::ifstream in(path, std::ios::binary);
-  if (!in) return std::string();
-  std::stringstream ss;
-  ss << in.rdbuf();
-  return ss.str();
-}
-
-struct Spec {
-  int op = 0;
-  std::vector<UsedCol> cols;
-  std::string expr, cond, key, select;
-  std::vector<std::string> more;  // multi-output compaction: expressions 1.. (expr is expression 0)
-  int topk_k = 0, topk_desc = 1;
-  bool aligned = false;
-  int groups = 0;  // compaction tile depth (row quads per thread), 0 = n/a
-  int dwaves = 0;  // compaction data waves per workgroup
-  int gblock = 0, gunroll = 0;  // row gather: threads per workgroup, quads per thread (0 = n/a)
-  int minmax = 0;        // SUM / GROUP BY builds that also track MIN / MAX
-  std::string custom;
-  std::string extra;  // diagnostic -D list from $WARPDB_EXTRA_DEFINES
-
-  std::string key_string() const {
-    std::ostringstream k;
-    k << "op=" << op << "|a=" << aligned << "|k=" << topk_k << "|d=" << topk_desc << "|cols=";
-    for (auto &c : cols) k << c.name << ':' << c.ctype << ';';
-    k << "|g=" << groups << "|dw=" << dwaves << "|mm=" << minmax << "|x=" << extra;
-    if (gblock) k << "|gb=" << gblock << "|gu=" << gunroll;
-    k << "|e=" << expr << "|c=" << cond << "|key=" << key << "|s=" << select << "|cu=" << custom;
-    for (size_t i = 0; i < more.size(); ++i) k << "|e" << i + 1 << "=" << more[i];
-    return k.str();
-  }
-
-  std::string source() const {
-    std::ostringstream s;
-    if (!custom.empty()) s << "// ---- custom.cu (prepended as src/jit.cpp:65-83 does)\n" << custom << "\n";
-    s << "// ---- generated by warpexec\n";
-    s << "#define WX_OP " << op << "\n";
-    if (groups)
-      s << "#define WX_COMPACT_GROUPS " << groups << "\n#define WX_COMPACT_DWAVES " << dwaves << "\n";
-    if (gblock) s << "#define WX_GATHER_BLOCK " << gblock << "\n#define WX_GATHER_UNROLL " << gunroll << "\n";
-    {  // WARPDB_EXTRA_DEFINES="A=1,B" (diagnostic builds only); a *DIAG*
-       // switch among them also opens the kernels' WX_DIAG umbrella
-      if (extra.find("DIAG") != std::string::npos && extra.find("WX_DIAG=") == std::string::npos)
-        s << "#define WX_DIAG 1\n";
-      std::string item;
-      std::istringstream in(extra);
-      while (std::getline(in, item, ',')) {
-        if (item.empty()) continue;
-        auto eq = item.find('=');
-        if (eq == std::string::npos) s << "#define " << item << " 1\n";
-        else s << "#define " << item.substr(0, eq) << " " << item.substr(eq + 1) << "\n";
-      }
-    }
-    s << "#define WX_COLS(X)";
-    for (size_t i = 0; i < cols.size(); ++i) s << " X(" << cols[i].name << ", " << cols[i].ctype << ", " << i << ")";
-    s << "\n";
-    s << "#define WX_ALIGNED16 " << (aligned ? 1 : 0) << "\n";
-    if (minmax) s << "#define WX_MINMAX 1\n";
-    if (!expr.empty()) s << "#define WX_EXPR (" << expr << ")\n";
-    if (!more.empty()) {
-      s << "#define WX_NOUT " << more.size() + 1 << "\n";
-      for (size_t i = 0; i < more.size(); ++i) s << "#define WX_EXPR" << i + 1 << " (" << more[i] << ")\n";
-    }
-    if (!cond.empty()) s << "#define WX_HAS_COND 1\n#define WX_COND (" << cond << ")\n";
-    if (!key.empty()) s << "#define WX_KEY (" << key << ")\n";
-    if (!select.empty()) s << "#define WX_HAS_SELECT 1\n#define WX_SELECT (" << select << ")\n";
-    else s << "#define WX_HAS_SELECT 0\n";
-    if (topk_k) s << "#define WX_TOPK_K " << topk_k << "\n#define WX_TOPK_DESC " << topk_desc << "\n";
-    s << "#line 1 \"wx_args.h\"\n" << kWxArgsSrc << "\n";
-    // wx_common.hip, then the kernel family's own sources (each guarded by
-    // its WX_OP), in the embedding order
-    for (const auto &src : kWxSources) {
-      const std::string n = src.name;
-      const bool want = n == "wx_common.hip" || (op == WX_OP_DENSE && n == "wx_dense.hip") ||
-                        (op == WX_OP_COMPACT && n == "wx_compact.hip") || (op == WX_OP_SUM && n == "wx_sum.hip") ||
-                        (op == WX_OP_COMPACT && !more.empty() && (n == "wx_select_args.h" || n == "wx_select.hip")) ||
-                        (op == WX_OP_GROUP && (n == "wx_group.hip" || n == "wx_group_part.hip" ||
-                                               n == "wx_group_rows.hip")) ||
-                        (op == WX_OP_TOPK && n == "wx_topk.hip") ||
-                        (op == WX_OP_GATHER && (n == "wx_gather_args.h" || n == "wx_gather.hip")) ||
-                        (op == WX_OP_UTIL && (n == "wx_util.hip" || n == "wx_radix.hip" || n == "wx_group_rows.hip"));
-      if (want) s << "#line 1 \"" << n << "\"\n" << src.text << "\n";
-    }
-    return s.str();
-  }
-};
-
-uint64_t fnv1a(const std::string &s) {
-  uint64_t h = 1469598103934665603ull;
-  for (unsigned char c : s) {
-    h ^= c;
-    h *= 1099511628211ull;
-  }
-  return h;
-}
-
-// Code-object cache: $WARPDB_KERNEL_CACHE, or .kernel_cache next to this
-// library (so objects built in one container travel with the tree); "off"
-// disables it.
-std::string cache_dir() {
-  std::string d = env_or("WARPDB_KERNEL_CACHE", "");
-  if (d == "off" || d == "0") return std::string();
-  if (d.empty()) {
-    Dl_info info;
-    if (dladdr(reinterpret_cast<void *>(&wx_abi_version), &info) && info.dli_fname) {
-      std::string lib = info.dli_fname;
-      auto slash = lib.find_last_of('/');
-      d = (slash == std::string::npos ? std::string(".") : lib.substr(0, slash)) + "/.kernel_cache";
-    }
-  }
-  return d;
-}
-
-void mkdirs(const std::string &d) {
-  std::string cur;
-  for (size_t i = 0; i < d.size(); ++i) {
-    cur += d[i];
-    if (d[i] == '/' && cur.size() > 1) mkdir(cur.c_str(), 0755);
-  }
-  mkdir(d.c_str(), 0755);
-}
-
-// Identity of the compiler behind the code-object cache: the hiprtc version
-// and the ROCm build string of the installation it comes from.
-const std::string &compiler_id() {
-  static const std::string id = [] {
-    int major = 0, minor = 0;
-    (void)hiprtcVersion(&major, &minor);
-    std::string v = "hiprtc " + std::to_string(major) + "." + std::to_string(minor);
-    std::ifstream in(env_or("ROCM_PATH", "/opt/rocm") + "/.info/version");
-    std::string rocm;
-    if (in && std::getline(in, rocm)) v += " rocm " + rocm;
-    return v;
-  }();
-  return id;
-}
-
-// Compile with hiprtc.  Options: gfx950 (the device's full target id),
-// -O3, no FP contraction (projections stay bit-identical to the CPU
-// evaluator), hardware f64 atomics.
-std::vector<char> compile_program(const std::string &src, const std::string &arch) {
-  const std::string arch_opt = "--offload-arch=" + arch;
-  std::vector<const char *> opts = {arch_opt.c_str(), "-O3", "-std=c++17", "-ffp-contract=off",
-                                    "-munsafe-fp-atomics"};
-  const std::string dir = cache_dir();
-  std::string path;
-  if (!dir.empty()) {
-    std::string keysrc = src;
-    for (auto o : opts) keysrc += std::string("\x01") + o;
-    keysrc += std::string("\x01") + compiler_id();  // a cached object from another hiprtc is never reused
-    char name[64];
-    std::snprintf(name, sizeof(name), "%016llx-%zu.co", (unsigned long long)fnv1a(keysrc), src.size());
-    path = dir + "/" + name;
-    std::ifstream in(path, std::ios::binary);
-    if (in) {
-      std::vector<char> code((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
-      if (!code.empty()) return code;
-    }
-  }
-  hiprtcProgram prog = nullptr;
-  if (hiprtcCreateProgram(&prog, src.c_str(), "warpexec_query.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS)
-    fail(WX_ERR_COMPILE, "HIPRTC error: hiprtcCreateProgram failed");
-  struct Guard {
-    hiprtcProgram p;
-    ~Guard() {
-      if (p) hiprtcDestroyProgram(&p);
-    }
-  } guard{prog};
-  hiprtcResult r = hiprtcCompileProgram(prog, (int)opts.size(), opts.data());
-  size_t log_size = 0;
-  hiprtcGetProgramLogSize(prog, &log_size);
-  std::string log(log_size, '\0');
-  if (log_size) hiprtcGetProgramLog(prog, &log[0]);
-  if (r != HIPRTC_SUCCESS)
-    fail(WX_ERR_COMPILE, std::string("Kernel compilation failed.\n") + hiprtcGetErrorString(r) + "\n" + log);
-  size_t code_size = 0;
-  if (hiprtcGetCodeSize(prog, &code_size) != HIPRTC_SUCCESS || !code_size)
-    fail(WX_ERR_COMPILE, "HIPRTC error: empty code object");
-  std::vector<char> code(code_size);
-  hiprtcGetCode(prog, code.data());
-  ++g_compiles;
-  if (!path.empty()) {
-    mkdirs(dir);
-    std::string tmp = path + ".tmp" + std::to_string(getpid()) + "." +
-                      std::to_string(std::hash<std::thread::id>()(std::this_thread::get_id()));
-    {
-      std::ofstream out(tmp, std::ios::binary);
-      out.write(code.data(), (std::streamsize)code.size());
-    }
-    std::rename(tmp.c_str(), path.c_str());
-  }
-  return code;
-}
-
-// NAME=value from a diagnostic define list ("A=1,B=2"), or dflt: the host
-// side of a geometry an A/B build changes (compaction and radix tiles)
-int define_value(const std::string &extra, const std::string &name, int dflt) {
-  std::string item;
-  std::istringstream in(extra);
-  int v = dflt;
-  while (std::getline(in, item, ','))
-    if (item.compare(0, name.size() + 1, name + "=") == 0) v = std::atoi(item.c_str() + name.size() + 1);
-  return v;
-}
-
-// Compaction geometry: 12 data waves x 4 row quads per thread, 12288-row
-// tiles (two 72 KB stage buffers; DESIGN.md 5.1, profiles/r01/
-// ablate_compact_deep.txt).  One module holds the pipelined kernel and the
-// one-tile-per-workgroup fallback; $WARPDB_COMPACT_SCHED=ticket selects the
-// fallback (a test hook: parity of both schedules).
-void compact_geometry(Spec &spec) {
-  // (a diagnostic build may set WX_COMPACT_GROUPS / _DWAVES in the define
-  // list; the host reads them back so its tile size matches the kernel's)
-  const std::string extra = env_or("WARPDB_EXTRA_DEFINES", "");
-  spec.groups = define_value(extra, "WX_COMPACT_GROUPS", 4);
-  spec.dwaves = define_value(extra, "WX_COMPACT_DWAVES", 12);
-  if (spec.groups < 1 || spec.dwaves < 1 || spec.dwaves > 15 ||
-      (int64_t)spec.dwaves * 64 * 4 * spec.groups * 12 > 150 * 1024)
-    fail(WX_ERR_INVALID, "compaction tile out of range (two stage buffers must fit the LDS)");
-}
-bool compact_ticket_sched() { return env_or("WARPDB_COMPACT_SCHED", "deep") == "ticket"; }
-
-// Multi-output compaction geometry (wx_select.hip): a staged row costs
-// 4 * nout + 2 bytes in each of the two stage buffers, so the tile shrinks
-// with the output count -- 3 row quads per thread and 10 / 7 / 5 data waves
-// for 2 / 3 / 4 outputs (7680 / 5376 / 3840 rows: 150 / 147 / 135 KiB), the
-// fastest of the geometries measured at 1e9 rows.
-// WX_COMPACT_GROUPS / _DWAVES of the define list override it as for the
-// single-output kernel.
-void select_geometry(Spec &spec, int nout) {
-  static const int kDwaves[WX_SELECT_MAX_OUT + 1] = {0, 10, 10, 7, 5};
-  const std::string extra = env_or("WARPDB_EXTRA_DEFINES", "");
-  spec.groups = define_value(extra, "WX_COMPACT_GROUPS", 3);
-  spec.dwaves = define_value(extra, "WX_COMPACT_DWAVES", kDwaves[nout]);
-  // (at most 8 quads per thread: the kernel keeps a thread's 4 * groups keep bits in one 32-bit word)
-  if (spec.groups < 1 || spec.groups > 8 || spec.dwaves < 1 || spec.dwaves > 15 ||
-      (int64_t)spec.dwaves * 64 * 4 * spec.groups * WX_SELECT_ROW_BYTES(nout) > WX_SELECT_LDS_BUDGET)
-    fail(WX_ERR_INVALID, "multi-output compaction tile out of range (at most 8 row quads per thread, and two "
-                         "stage buffers must fit the LDS)");
-}
-
-// Target id of the MI355X when no device is visible (builds in the CPU
-// container); matches hipDeviceProp_t::gcnArchName on the GPU box, so cached
-// code objects built here are reused there.
-std::string default_arch() { return env_or("WARPDB_ARCH", "gfx950:sramecc+:xnack-"); }
-
-
-
-std::shared_ptr<Module> get_module(int dev, const Spec &spec, bool load) {
-  const std::string key = spec.key_string();
-  std::string arch;
-  {
-    Lock lk(g_mu);
-    DeviceState &d = device_state(dev, load);
-    auto it = d.modules.find(key);
-    if (it != d.modules.end() && (!load || it->second->mod)) {
-      ++g_hits;
-      return it->second;
-    }
-    arch = d.arch.empty() ? default_arch() : d.arch;
-  }
-  // compile and load outside the lock; if another thread got there first,
-  // keep its module
-  const int64_t compiles_before = g_compiles;
-  std::vector<char> code = compile_program(spec.source(), arch);
-  if (g_compiles != compiles_before && std::getenv("WARPDB_DEBUG"))  // a code-object cache miss
-    std::fprintf(stderr, "[warpexec] hiprtc compile (cache miss): %s\n", key.substr(0, 300).c_str());
-  auto m = std::make_shared<Module>();
-  if (load) WX_HIP(hipModuleLoadData(&m->mod, code.data()));
-  if (!load) return m;
-  Lock lk(g_mu);
-  DeviceState &d = device_state(dev, load);
-  auto it = d.modules.find(key);
-  if (it != d.modules.end() && it->second->mod) {
-    (void)hipModuleUnload(m->mod);
-    return it->second;
-  }
-  d.modules[key] = m;
-  return m;
-}
-
-void launch(hipFunction_t f, unsigned grid, void *args, hipStream_t s, bool timed = false,
-            unsigned block = WX_BLOCK, unsigned shmem = 0) {
-  void *params[] = {args};
-  hipEvent_t ea = nullptr, eb = nullptr;
-  int dev = 0;
-  if (timed) {
-    WX_HIP(hipGetDevice(&dev));
-    auto take = [dev](hipEvent_t &e) {
-      Lock lk(g_mu);
-      auto &pool = g_event_pool[dev];  // events belong to the device they were created on
-      if (!pool.empty()) {
-        e = pool.back();
-        pool.pop_back();
-      } else {
-        // timing only: no system-scope fence (cache writeback + invalidate)
-        // when the event is recorded, so timing a launch does not slow the
-        // stream it times
-        WX_HIP(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
-      }
-    };
-    take(ea);
-    take(eb);
-    WX_HIP(hipEventRecord(ea, s));
-  }
-  WX_HIP(hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, shmem, s, params, nullptr));
-  if (timed) {
-    WX_HIP(hipEventRecord(eb, s));
-    Lock lk(g_mu);
-    g_timed.push_back({ea, eb, dev});
-  }
-}
-
-bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
-bool cols_aligned(const wx_table *t, const std::vector<UsedCol> &cols) {
-  for (auto &c : cols)
-    if (!aligned16(t->cols[c.table_index].d_ptr)) return false;
-  return true;
-}
-
-void fill_cols(const wx_table *t, const std::vector<UsedCol> &cols, const void **dst) {
-  for (int i = 0; i < WX_MAX_COLS; ++i) dst[i] = nullptr;
-  for (size_t i = 0; i < cols.size(); ++i) dst[i] = t->cols[cols[i].table_index].d_ptr;
-}
-
-void check_table(const wx_table *t) {
-  if (!t) fail(WX_ERR_INVALID, "null table");
-  if (t->n_rows < 0) fail(WX_ERR_INVALID, "negative row count");
-  if (t->n_cols < 0 || (t->n_cols > 0 && !t->cols)) fail(WX_ERR_INVALID, "bad column list");
-}
-
-wx_launch default_launch() {
-  wx_launch L;
-  L.device = 0;
-  L.stream = nullptr;
-  L.custom_src = nullptr;
-  L.flags = 0;
-  return L;
-}
-
-// Read (and clear) device error bits of a workspace; throws on any.
-std::string lookback_report(const uint64_t *d) {
-  // d = ctrs[3..7]: claim, {kind | launch epoch << 8 | digit << 16 | pass << 32}, waiting tile,
-  // waited-on tile, the status word seen (wx_args.h WX_LBD_*)
-  if (!d[0]) return " (no report recorded)";
-  const unsigned kind = (unsigned)(d[1] & 0xff), epoch = (unsigned)((d[1] >> 8) & 0xff);
-  const unsigned digit = (unsigned)((d[1] >> 16) & 0xffff), pass = (unsigned)(d[1] >> 32);
-  const unsigned seen_epoch = (unsigned)(d[4] >> 58), seen_flag = (unsigned)((d[4] >> 56) & 3);
-  char b[320];
-  if (kind == WX_LBD_RADIX)
-    std::snprintf(b, sizeof b,
-                  ": radix pass %u tile %llu digit %u waited on tile %llu, whose word 0x%016llx has epoch %u flag %u "
-                  "(launch epoch %u)",
-                  pass, (unsigned long long)d[2], digit, (unsigned long long)d[3], (unsigned long long)d[4],
-                  seen_epoch, seen_flag, epoch);
-  else
-    std::snprintf(b, sizeof b,
-                  ": compaction tile %llu waited on tile %llu, whose word 0x%016llx has epoch %u flag %u "
-                  "(launch epoch %u)",
-                  (unsigned long long)d[2], (unsigned long long)d[3], (unsigned long long)d[4], seen_epoch, seen_flag,
-                  epoch);
-  return b;
-}
-
-void check_errors(Workspace &w) {
-  // both error words (and the look-back report) through one pinned buffer
-  // and one stream sync (pageable synchronous copies cost ≈ 10 µs each)
-  if (!w.h_err) WX_HIP(hipHostMalloc(reinterpret_cast<void **>(&w.h_err), 8 * sizeof(uint64_t)));
-  for (int i = 0; i < 8; ++i) w.h_err[i] = 0;
-  // h_err[0..6] = ctrs[1..7], h_err[7] = g_ctrs[1]
-  WX_HIP(hipMemcpyAsync(&w.h_err[0], static_cast<uint64_t *>(w.ctrs.p) + 1, 7 * 8, hipMemcpyDeviceToHost, w.stream));
-  if (w.g_ctrs.p)
-    WX_HIP(hipMemcpyAsync(&w.h_err[7], static_cast<uint64_t *>(w.g_ctrs.p) + 1, 8, hipMemcpyDeviceToHost, w.stream));
-  WX_HIP(hipStreamSynchronize(w.stream));
-  const uint64_t bits = w.h_err[0] | w.h_err[7];
-  if (!bits) return;
-  const std::string report = lookback_report(&w.h_err[2]);
-  // clear on the workspace stream: ordered before the next launch that reads them
-  WX_HIP(hipMemsetAsync(static_cast<uint64_t *>(w.ctrs.p) + 1, 0, 8, w.stream));
-  WX_HIP(hipMemsetAsync(static_cast<uint64_t *>(w.ctrs.p) + WX_LBD_BASE, 0, 5 * 8, w.stream));
-  if (w.g_ctrs.p) WX_HIP(hipMemsetAsync(static_cast<uint64_t *>(w.g_ctrs.p) + 1, 0, 8, w.stream));
-  if (bits & WX_DEVERR_LOOKBACK) fail(WX_ERR_INTERNAL, "device look-back timed out (results invalid)" + report);
-  if (bits & WX_DEVERR_CAPACITY) fail(WX_ERR_CAPACITY, "group table / output capacity exceeded");
-  if (bits & WX_DEVERR_UNSUPPORTED)
-    fail(WX_ERR_UNSUPPORTED, "more than 4096 distinct GROUP BY keys outside the dense key window");
-  if (bits & WX_DEVERR_INTERNAL_KEY)
-    fail(WX_ERR_INTERNAL, "GROUP BY consistency check failed (a key outside its planned range, a work-item "
-                          "overflow, or row counts that disagree between passes)");
-  fail(WX_ERR_INTERNAL, "device error bits set");
-}
-
-// Workgroups per CU for the grid-stride kernels: the per-op value measured
-// best (profiles/r01/ablate_stream.txt).
-int grid_per_cu(int per_op) { return per_op; }
-
-unsigned grid_for(int64_t work_items, int cus, int per_cu) {
-  int64_t g = (work_items + WX_BLOCK - 1) / WX_BLOCK;
-  const int64_t cap = (int64_t)cus * per_cu;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (unsigned)g;
-}
-
-template <typename F>
-wx_status guarded(char *err, size_t errlen, F &&body) {
-  if (err && errlen) err[0] = 0;
-  try {
-    body();
-    return WX_OK;
-  } catch (const WxError &e) {
-    if (err && errlen) std::snprintf(err, errlen, "%s", e.msg.c_str());
-    return e.st;
-  } catch (const std::bad_alloc &) {
-    if (err && errlen) std::snprintf(err, errlen, "out of host memory");
-    return WX_ERR_INTERNAL;
-  } catch (const std::exception &e) {
-    if (err && errlen) std::snprintf(err, errlen, "%s", e.what());
-    return WX_ERR_INTERNAL;
-  }
-}
-
-// ----------------------------------------------------------- operations
-void do_project_filter(const wx_table *t, const char *expr, const char *cond, const wx_launch *Lp, int32_t mode,
-                       float *d_out_vals, void *d_out_idx, int32_t idx_bytes, int64_t row_base,
-                       int64_t *d_count, int64_t *h_count) {
-  check_table(t);
-  const wx_launch L = Lp ? *Lp : default_launch();
-  if (blank(expr)) fail(WX_ERR_INVALID, "Empty query expression");
-  if (mode < WX_MODE_DENSE || mode > WX_MODE_COMPACT) fail(WX_ERR_INVALID, "unknown mode");
-  if (mode == WX_MODE_COMPACT && d_out_idx && idx_bytes != 4 && idx_bytes != 8)
-    fail(WX_ERR_INVALID, "idx_bytes must be 4 or 8");
-  if (mode == WX_MODE_COMPACT && d_out_idx && idx_bytes == 4 && row_base + t->n_rows > INT32_MAX)
-    fail(WX_ERR_INVALID, "row indices exceed int32; use idx_bytes = 8");
-  if (mode != WX_MODE_COMPACT && !d_out_vals && t->n_rows) fail(WX_ERR_INVALID, "null output buffer");
-  // No WHERE and no row indices wanted: every row passes in order, so the
-  // compacted values are the dense projection (no ballots, no look-back)
-  const bool every_row = mode == WX_MODE_COMPACT && blank(cond) && !d_out_idx;
-  Spec spec;
-  spec.op = mode == WX_MODE_COMPACT && !every_row ? WX_OP_COMPACT : WX_OP_DENSE;
-  if (spec.op == WX_OP_COMPACT) compact_geometry(spec);
-  spec.cols = used_columns(t, {expr, cond});
-  spec.expr = one_line(expr);
-  spec.cond = blank(cond) ? std::string() : one_line(cond);
-  spec.custom = read_custom(&L);
-  spec.extra = env_or("WARPDB_EXTRA_DEFINES", "");
-  spec.aligned = cols_aligned(t, spec.cols) && (spec.op != WX_OP_DENSE || aligned16(d_out_vals));
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  auto mod = get_module(L.device, spec, true);
-  DeviceState &d = device_state(L.device, true);
-  Workspace &w = workspace(L.device, s);
-  OpLock op_lock(w.op_mu);
-  const bool timed = (L.flags & WX_F_TIME) != 0;
-  int64_t *count_dst = d_count;
-  if (spec.op == WX_OP_DENSE) {
-    if (t->n_rows > 0 && d_out_vals) {  // (no values buffer: a count-only every_row call)
-      WxDenseArgs a;
-      fill_cols(t, spec.cols, a.col);
-      a.out = d_out_vals;
-      a.n_rows = t->n_rows;
-      a.fill = mode == WX_MODE_DENSE_FILL;
-      // 4 quads per thread per span (WX_UNROLL), contiguous spans, 3 per CU
-      const int64_t spans = ((t->n_rows + 3) / 4 + 4 * WX_BLOCK - 1) / (4 * WX_BLOCK);
-      launch(mod->fn("wx_project_dense"), grid_for(spans * WX_BLOCK, d.cus, grid_per_cu(3)), &a, s, timed);
-    }
-    if (h_count || d_count) {
-      // the reference's dense contract has no count; report the row count
-      // (every_row: all rows passed).  Two 32-bit fills, so nothing on the
-      // stream reads from this call's (pageable) stack after it returns.
-      if (d_count) {
-        const uint64_t n = (uint64_t)t->n_rows;
-        WX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(d_count), (int)(uint32_t)n, 1, s));
-        WX_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(reinterpret_cast<uint32_t *>(d_count) + 1),
-                                 (int)(uint32_t)(n >> 32), 1, s));
-      }
-      if (h_count) *h_count = t->n_rows;
-    }
-  } else {
-    if (!count_dst && h_count) {
-      ensure(w, w.count_tmp, 8, false);
-      count_dst = static_cast<int64_t *>(w.count_tmp.p);
-    }
-    const int64_t tile_rows = (int64_t)spec.dwaves * 64 * 4 * spec.groups;
-    const int64_t n_tiles = (t->n_rows + tile_rows - 1) / tile_rows;
-    if (n_tiles == 0) {
-      if (count_dst) WX_HIP(hipMemsetAsync(count_dst, 0, 8, s));
-    } else {
-      if (n_tiles > 0xffffffffll) fail(WX_ERR_INVALID, "table too large for one launch");
-      // No per-query clearing: the status words carry the launch's epoch
-      // (a fresh array starts at epoch 0 = all zero; one memset every 63
-      // launches), and the last workgroup to retire returns the ticket to 0.
-      void *old_status = w.status.p;
-      ensure(w, w.status, (size_t)(n_tiles + 1) * 8, true);
-      if (w.status.p != old_status) w.cs_epoch = 0;
-      if (++w.cs_epoch > WX_CS_EPOCHS) {
-        WX_HIP(hipMemsetAsync(w.status.p, 0, w.status.bytes, s));
-        w.cs_epoch = 1;
-      }
-      WxCompactArgs a;
-      fill_cols(t, spec.cols, a.col);
-      a.out_val = d_out_vals;
-      a.out_idx = d_out_idx;
-      a.status = static_cast<wx_u64 *>(w.status.p);
-      a.ctrs = static_cast<wx_u64 *>(w.ctrs.p);
-      a.count_out = reinterpret_cast<wx_i64 *>(count_dst);
-      a.n_rows = t->n_rows;
-      a.n_tiles = n_tiles;
-      a.row_base = row_base;
-      a.idx64 = idx_bytes == 8;
-      a.epoch = w.cs_epoch;
-      a.diag = nullptr;
-      const bool timeline = spec.extra.find("WX_DIAG_TIMELINE") != std::string::npos;  // diagnostics only
-      if (!compact_ticket_sched()) {
-        // Persistent pipelined kernel, tiles from a ticket counter: any grid
-        // size is correct (a workgroup that starts late finds the tickets
-        // taken and exits); one workgroup per CU at the occupancy the
-        // kernel's LDS allows is what keeps every CU streaming.
-        hipFunction_t fn = mod->fn("wx_project_compact_deep");
-        int per_cu = 0, lds = 0;
-        const unsigned cblock = (unsigned)(spec.dwaves + 1) * 64;
-        WX_HIP(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, cblock, 0));
-        WX_HIP(hipFuncGetAttribute(&lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, fn));
-        const int lds_limit = lds > 0 ? (160 * 1024) / lds : 64;
-        const int bpc = std::max(1, std::min(per_cu, lds_limit));
-        const unsigned grid = (unsigned)std::min<int64_t>(n_tiles, (int64_t)d.cus * bpc);
-        if (std::getenv("WARPDB_DEBUG"))
-          std::fprintf(stderr, "[warpexec] compact: occupancy %d/CU, lds %d B, lds_limit %d, bpc %d, grid %u, tiles %lld\n",
-                       per_cu, lds, lds_limit, bpc, grid, (long long)n_tiles);
-        if (timeline) {
-          ensure(w, w.diag, (size_t)grid * 16 * 8, false);
-          WX_HIP(hipMemsetAsync(w.diag.p, 0, (size_t)grid * 16 * 8, s));
-          a.diag = static_cast<wx_u64 *>(w.diag.p);
-        }
-        launch(fn, grid, &a, s, timed, cblock);
-        if (timeline) {  // per-workgroup entry / first tile / first evaluation / end, 10 ns ticks -> us
-          std::vector<wx_u64> h((size_t)grid * 16);
-          WX_HIP(hipMemcpyAsync(h.data(), w.diag.p, h.size() * 8, hipMemcpyDeviceToHost, s));
-          WX_HIP(hipStreamSynchronize(s));
-          wx_u64 t0 = ~0ull;
-          for (unsigned b = 0; b < grid; ++b) t0 = std::min(t0, h[(size_t)b * 16]);
-          const char *names[4] = {"entry", "tickets", "eval0", "end"};
-          std::fprintf(stderr, "[warpexec] timeline grid %u tiles %lld:", grid, (long long)n_tiles);
-          for (int i = 0; i < 4; ++i) {
-            std::vector<double> v;
-            for (unsigned b = 0; b < grid; ++b) v.push_back((double)(h[(size_t)b * 16 + i] - t0) / 100.0);
-            std::sort(v.begin(), v.end());
-            std::fprintf(stderr, " %s min %.1f p50 %.1f max %.1f |", names[i], v.front(), v[v.size() / 2], v.back());
-          }
-          int64_t tmin = INT64_MAX, tmax = 0;
-          for (unsigned b = 0; b < grid; ++b) {
-            tmin = std::min<int64_t>(tmin, (int64_t)h[(size_t)b * 16 + 4]);
-            tmax = std::max<int64_t>(tmax, (int64_t)h[(size_t)b * 16 + 4]);
-          }
-          std::fprintf(stderr, " tiles/wg %lld..%lld (us)\n", (long long)tmin, (long long)tmax);
-        }
-      } else {
-        launch(mod->fn("wx_project_compact_ticket"), (unsigned)n_tiles, &a, s, timed, (unsigned)spec.dwaves * 64);
-      }
-    }
-  }
-  if ((L.flags & WX_F_SYNC) || h_count) check_errors(w);
-  if (h_count && spec.op == WX_OP_COMPACT) WX_HIP(hipMemcpy(h_count, count_dst, 8, hipMemcpyDeviceToHost));
-}
-
-// The argument checks of a multi-output call that need no device (n_exprs
-// in range, no blank expression), and the module of n_exprs >= 2 outputs.
-void check_select_exprs(const char *const *exprs, int32_t n_exprs) {
-  if (n_exprs < 1 || n_exprs > WX_MAX_OUTPUTS || !exprs)
-    fail(WX_ERR_INVALID, "n_exprs must be between 1 and " + std::to_string(WX_MAX_OUTPUTS));
-  for (int32_t j = 0; j < n_exprs; ++j)
-    if (blank(exprs[j])) fail(WX_ERR_INVALID, "Empty query expression");
-}
-
-Spec select_spec(const wx_table *t, const char *const *exprs, int32_t n_exprs, const char *cond, const wx_launch &L) {
-  Spec spec;
-  spec.op = WX_OP_COMPACT;
-  select_geometry(spec, n_exprs);
-  std::vector<const char *> all(exprs, exprs + n_exprs);
-  all.push_back(cond);
-  spec.cols = used_columns(t, all);
-  spec.expr = one_line(exprs[0]);
-  for (int32_t j = 1; j < n_exprs; ++j) spec.more.push_back(one_line(exprs[j]));
-  spec.cond = blank(cond) ? std::string() : one_line(cond);
-  spec.custom = read_custom(&L);
-  spec.extra = env_or("WARPDB_EXTRA_DEFINES", "");
-  spec.aligned = cols_aligned(t, spec.cols);
-  return spec;
-}
-
-// n_exprs outputs of one filtered result in one pass (wx_select.hip); one
-// expression is the single-output call itself.  With no WHERE every row
-// passes through the same kernel.
-void do_project_filter_multi(const wx_table *t, const char *const *exprs, int32_t n_exprs, const char *cond,
-                             const wx_launch *Lp, int32_t mode, float *const *d_out_vals, void *d_out_idx,
-                             int32_t idx_bytes, int64_t row_base, int64_t *d_count, int64_t *h_count) {
-  check_table(t);
-  check_select_exprs(exprs, n_exprs);
-  if (n_exprs == 1) {
-    do_project_filter(t, exprs[0], cond, Lp, mode, d_out_vals ? d_out_vals[0] : nullptr, d_out_idx, idx_bytes,
-                      row_base, d_count, h_count);
-    return;
-  }
-  const wx_launch L = Lp ? *Lp : default_launch();
-  if (mode < WX_MODE_DENSE || mode > WX_MODE_COMPACT) fail(WX_ERR_INVALID, "unknown mode");
-  if (mode != WX_MODE_COMPACT) fail(WX_ERR_UNSUPPORTED, "more than one output needs WX_MODE_COMPACT");
-  if (d_out_idx && idx_bytes != 4 && idx_bytes != 8) fail(WX_ERR_INVALID, "idx_bytes must be 4 or 8");
-  if (d_out_idx && idx_bytes == 4 && row_base + t->n_rows > INT32_MAX)
-    fail(WX_ERR_INVALID, "row indices exceed int32; use idx_bytes = 8");
-  const Spec spec = select_spec(t, exprs, n_exprs, cond, L);
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  auto mod = get_module(L.device, spec, true);
-  DeviceState &d = device_state(L.device, true);
-  Workspace &w = workspace(L.device, s);
-  OpLock op_lock(w.op_mu);
-  const bool timed = (L.flags & WX_F_TIME) != 0;
-  int64_t *count_dst = d_count;
-  if (!count_dst && h_count) {
-    ensure(w, w.count_tmp, 8, false);
-    count_dst = static_cast<int64_t *>(w.count_tmp.p);
-  }
-  const int64_t tile_rows = (int64_t)spec.dwaves * 64 * 4 * spec.groups;
-  const int64_t n_tiles = (t->n_rows + tile_rows - 1) / tile_rows;
-  if (n_tiles == 0) {
-    if (count_dst) WX_HIP(hipMemsetAsync(count_dst, 0, 8, s));
-  } else {
-    if (n_tiles > 0xffffffffll) fail(WX_ERR_INVALID, "table too large for one launch");
-    // the status words and the ticket are the single-output kernel's (epoch
-    // tags, no per-query clearing: see do_project_filter)
-    void *old_status = w.status.p;
-    ensure(w, w.status, (size_t)(n_tiles + 1) * 8, true);
-    if (w.status.p != old_status) w.cs_epoch = 0;
-    if (++w.cs_epoch > WX_CS_EPOCHS) {
-      WX_HIP(hipMemsetAsync(w.status.p, 0, w.status.bytes, s));
-      w.cs_epoch = 1;
-    }
-    WxSelectArgs a;
-    fill_cols(t, spec.cols, a.c.col);
-    a.c.out_val = nullptr;
-    a.c.out_idx = d_out_idx;
-    a.c.status = static_cast<wx_u64 *>(w.status.p);
-    a.c.ctrs = static_cast<wx_u64 *>(w.ctrs.p);
-    a.c.count_out = reinterpret_cast<wx_i64 *>(count_dst);
-    a.c.n_rows = t->n_rows;
-    a.c.n_tiles = n_tiles;
-    a.c.row_base = row_base;
-    a.c.idx64 = idx_bytes == 8;
-    a.c.epoch = w.cs_epoch;
-    a.c.diag = nullptr;
-    for (int j = 0; j < WX_SELECT_MAX_OUT; ++j) a.out_val[j] = j < n_exprs && d_out_vals ? d_out_vals[j] : nullptr;
-    if (!compact_ticket_sched()) {
-      hipFunction_t fn = mod->fn("wx_select_compact_deep");
-      int per_cu = 0, lds = 0;
-      const unsigned cblock = (unsigned)(spec.dwaves + 1) * 64;
-      WX_HIP(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, cblock, 0));
-      WX_HIP(hipFuncGetAttribute(&lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, fn));
-      const int lds_limit = lds > 0 ? (160 * 1024) / lds : 64;
-      const int bpc = std::max(1, std::min(per_cu, lds_limit));
-      const unsigned grid = (unsigned)std::min<int64_t>(n_tiles, (int64_t)d.cus * bpc);
-      if (std::getenv("WARPDB_DEBUG"))
-        std::fprintf(stderr, "[warpexec] select x%d: occupancy %d/CU, lds %d B, bpc %d, grid %u, tiles %lld\n", n_exprs,
-                     per_cu, lds, bpc, grid, (long long)n_tiles);
-      launch(fn, grid, &a, s, timed, cblock);
-    } else {
-      launch(mod->fn("wx_select_compact_ticket"), (unsigned)n_tiles, &a, s, timed, (unsigned)spec.dwaves * 64);
-    }
-  }
-  if ((L.flags & WX_F_SYNC) || h_count) check_errors(w);
-  if (h_count) WX_HIP(hipMemcpy(h_count, count_dst, 8, hipMemcpyDeviceToHost));
-}
-
-void do_reduce_sum(const wx_table *t, const char *expr, const char *cond, const wx_launch *Lp, void *d_out,
-                   double *h_sum, int64_t *h_count, bool minmax = false, wx_stats *h_stats = nullptr) {
-  check_table(t);
-  const wx_launch L = Lp ? *Lp : default_launch();
-  if (blank(expr)) fail(WX_ERR_INVALID, "Empty query expression");
-  Spec spec;
-  spec.op = WX_OP_SUM;
-  spec.minmax = minmax ? 1 : 0;
-  spec.cols = used_columns(t, {expr, cond});
-  spec.expr = one_line(expr);
-  spec.cond = blank(cond) ? std::string() : one_line(cond);
-  spec.custom = read_custom(&L);
-  spec.extra = env_or("WARPDB_EXTRA_DEFINES", "");
-  spec.aligned = cols_aligned(t, spec.cols);
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  auto mod = get_module(L.device, spec, true);
-  DeviceState &d = device_state(L.device, true);
-  Workspace &w = workspace(L.device, s);
-  OpLock op_lock(w.op_mu);
-  const unsigned grid = grid_for((t->n_rows + 3) / 4, d.cus, grid_per_cu(8));  // profiles/r01/ablate_stream.txt
-  ensure(w, w.part_sum, grid * 8, false);
-  ensure(w, w.part_cnt, grid * 8, false);
-  if (minmax) {
-    ensure(w, w.part_min, grid * 4, false);
-    ensure(w, w.part_max, grid * 4, false);
-  }
-  void *out = d_out;
-  if (!out) {
-    ensure(w, w.sum_out, sizeof(wx_stats), false);
-    out = w.sum_out.p;
-  }
-  WxSumArgs a;
-  fill_cols(t, spec.cols, a.col);
-  a.part_sum = static_cast<double *>(w.part_sum.p);
-  a.part_cnt = static_cast<wx_i64 *>(w.part_cnt.p);
-  a.part_min = static_cast<wx_u32 *>(w.part_min.p);
-  a.part_max = static_cast<wx_u32 *>(w.part_max.p);
-  a.n_rows = t->n_rows;
-  launch(mod->fn("wx_reduce_sum"), grid, &a, s, (L.flags & WX_F_TIME) != 0);
-  WxSumFinArgs f;
-  f.part_sum = a.part_sum;
-  f.part_cnt = a.part_cnt;
-  f.part_min = a.part_min;
-  f.part_max = a.part_max;
-  f.out = static_cast<double *>(out);
-  f.n_parts = (int)grid;
-  f.count_f64 = (L.flags & WX_F_F64_COUNTS) && d_out && !minmax ? 1 : 0;
-  void *params[] = {&f};
-  WX_HIP(hipModuleLaunchKernel(mod->fn("wx_sum_finalize"), 1, 1, 1, 1024, 1, 1, 0, s, params, nullptr));  // WX_SFIN_BLOCK
-  if ((L.flags & WX_F_SYNC) || h_sum || h_count || h_stats) check_errors(w);
-  if (h_sum || h_count || h_stats) {
-    wx_stats host;
-    WX_HIP(hipMemcpy(&host, out, minmax ? sizeof(wx_stats) : 16, hipMemcpyDeviceToHost));
-    if (h_sum) *h_sum = host.sum;
-    if (f.count_f64) {
-      double c;
-      std::memcpy(&c, &host.count, 8);
-      host.count = (int64_t)c;
-    }
-    if (h_count) *h_count = host.count;
-    if (h_stats) *h_stats = host;
-  }
-}
-
-std::shared_ptr<Module> util_module(int dev, bool load, const std::string &more = "");
-
-// Ascending sort of npad (a power of two >= WX_SORT_LDS) 64-bit keys in
-// place: LDS passes for spans up to WX_SORT_LDS, global passes above.
-void bitonic_u64(int dev, wx_u64 *keys, int64_t npad, hipStream_t s) {
-  auto mod = util_module(dev, true, "");
-  DeviceState &d = device_state(dev, true);
-  const unsigned lds_blocks = (unsigned)(npad / WX_SORT_LDS);
-  WxSortPassArgs q;
-  q.keys = keys;
-  q.npad = npad;
-  q.k = 2;
-  q.j = WX_SORT_LDS;
-  launch(mod->fn("wx_bitonic_lds"), lds_blocks, &q, s);
-  for (int64_t k = 2 * WX_SORT_LDS; k <= npad; k <<= 1) {
-    for (int64_t j = k >> 1; j >= WX_SORT_LDS; j >>= 1) {
-      WxSortPassArgs gp;
-      gp.keys = keys;
-      gp.npad = npad;
-      gp.k = k;
-      gp.j = j;
-      launch(mod->fn("wx_bitonic_global"), grid_for(npad, d.cus, 8), &gp, s);
-    }
-    WxSortPassArgs lp;
-    lp.keys = keys;
-    lp.npad = npad;
-    lp.k = k;
-    lp.j = k;
-    launch(mod->fn("wx_bitonic_lds"), lds_blocks, &lp, s);
-  }
-}
-
-uint32_t next_pow2(uint64_t v) {
-  uint64_t p = 1;
-  while (p < v) p <<= 1;
-  return (uint32_t)std::min<uint64_t>(p, 1u << 30);
-}
-
-// Range-partitioned GROUP BY (wx_group_part.hip), for a
-// caller expecting many groups (capacity > WX_GROUP_HSORT_MAX) on >= 2^20
-// rows.  The key range comes from the previous call over the same table and
-// expressions (memo), else from a 65 536-row sample (widened by an eighth on
-// each side), else from an exact min / max pass.  A range within the LDS
-// window runs the window kernel with the window placed on it (the global hash
-// still catches any key outside: no further host read); a range up to
-// 2^24 keys runs the partitioned kernels, which count the rows outside the
-// planned range: the host reads that summary once at the end (the one host
-// synchronisation of the partitioned form) and, when some row was outside,
-// re-plans from the exact range the same pass measured.  Anything wider
-// keeps the window + global hash.
-// below 2^20 rows the window + hash path is as fast; $WARPDB_GP_MIN_ROWS
-// lowers the floor (test hook: small reference fixtures through this path)
-int64_t gp_min_rows() {
-  const char *v = std::getenv("WARPDB_GP_MIN_ROWS");
-  return (v && *v) ? std::atoll(v) : (1 << 20);
-}
-#define WX_GP_STAGE_MAX_PARTS 2048  // the tile scan: two partitions per thread (wx_group_part.hip WX_GP_STAGE_MAXP)
-#define WX_GP_AGG_DIR_WORDS 4096    // directory words the aggregation stages in LDS (WX_GP_DIRCH)
-
-// row quads per thread per tile: the kernel's WX_GP_SUNROLL
-int gp_sunroll() { return 4; }
-// the tile kernel's workgroup (wx_group_part.hip WX_GP_TBLOCK) and rows per tile
-#define WX_GP_TBLOCK 1024
-int64_t gp_tile_rows() { return (int64_t)WX_GP_TBLOCK * 4 * gp_sunroll(); }
-
-// 8192 keys per partition (96 KB of LDS per aggregating workgroup)
-int gp_shift() { return 13; }
-int64_t gp_max_span() { return (int64_t)WX_GP_STAGE_MAX_PARTS << gp_shift(); }
-
-// wx_group_sum's workgroup size (512 at two per CU: profiles/r03/abl_group_grid.txt)
-int gp_gblock() { return WX_GBLOCK; }
-
-struct KeyRange {
-  bool any = false;
-  int64_t lo = 0, hi = -1, passing = 0;
-  int64_t span() const { return hi - lo + 1; }
-};
-
-// (min, max, passing) over the per-workgroup words mm[4g .. 4g+2]
-KeyRange reduce_mm(const int64_t *h, int64_t groups) {
-  KeyRange r;
-  int64_t mn = INT32_MAX, mx = INT32_MIN;
-  for (int64_t g = 0; g < groups; ++g) {
-    if (!h[4 * g + 2]) continue;
-    mn = std::min(mn, h[4 * g]);
-    mx = std::max(mx, h[4 * g + 1]);
-    r.passing += h[4 * g + 2];
-  }
-  if (r.passing) {
-    r.any = true;
-    r.lo = mn;
-    r.hi = mx;
-  }
-  return r;
-}
-
-KeyRange read_mm(Workspace &w, hipStream_t s, int64_t groups) {
-  std::vector<int64_t> h((size_t)groups * 4);
-  WX_HIP(hipMemcpyAsync(h.data(), w.gp_mm.p, h.size() * 8, hipMemcpyDeviceToHost, s));
-  WX_HIP(hipStreamSynchronize(s));
-  return reduce_mm(h.data(), groups);
-}
-
-// the range of a strided 65 536-row sample (one host read)
-KeyRange sample_keys(const wx_table *t, const std::vector<UsedCol> &cols, Module *mod, Workspace &w, hipStream_t s,
-                     bool timed) {
-  const unsigned grid = 64;
-  ensure(w, w.gp_mm, (size_t)grid * 32, false);
-  WxGroupPartArgs a{};
-  fill_cols(t, cols, a.col);
-  a.n_rows = t->n_rows;
-  a.mm = static_cast<wx_i64 *>(w.gp_mm.p);
-  launch(mod->fn("wx_group_part_sample"), grid, &a, s, timed, WX_GP_BLOCK);
-  return read_mm(w, s, grid);
-}
-
-// exact (min, max) key and passing rows over the whole table (one host read);
-// WX_GP_BLOCK threads over contiguous ranges of >= 4096 rows
-KeyRange probe_keys(const wx_table *t, const std::vector<UsedCol> &cols, Module *mod, DeviceState &d, Workspace &w,
-                    hipStream_t s, bool timed) {
-  int64_t G = std::min<int64_t>((int64_t)d.cus, std::max<int64_t>(1, (t->n_rows + 4095) / 4096));
-  int64_t rpw = ((t->n_rows + G - 1) / G + 3) & ~3ll;
-  G = (t->n_rows + rpw - 1) / rpw;
-  ensure(w, w.gp_mm, (size_t)G * 32, false);
-  WxGroupPartArgs a{};
-  fill_cols(t, cols, a.col);
-  a.n_rows = t->n_rows;
-  a.rows_per_wg = rpw;
-  a.mm = static_cast<wx_i64 *>(w.gp_mm.p);
-  launch(mod->fn("wx_group_part_minmax"), (unsigned)G, &a, s, timed, WX_GP_BLOCK);
-  return read_mm(w, s, G);
-}
-
-// One partitioned pass for keys [lo, lo + P << shift): tiles -> plan -> agg
-// -> count -> scan2 -> emit, then the summary read (passing rows, rows
-// outside the range, min key, max key).  Nothing is aggregated or emitted
-// when some row was outside (the caller re-plans).
-struct GpSummary {
-  int64_t passing = 0, outside = 0, mn = 0, mx = -1;
-};
-
-GpSummary group_partitioned(const wx_table *t, const std::vector<UsedCol> &cols, Module *mod, DeviceState &d,
-                            Workspace &w, hipStream_t s, bool timed, int64_t lo, int64_t span, int64_t capacity,
-                            int32_t *d_keys, double *d_sums, int64_t *d_counts, int64_t *ng) {
-  const int shift = gp_shift();
-  const int64_t B = 1ll << shift;
-  const int P = (int)((span + B - 1) >> shift);
-  if (P < 1 || P > WX_GP_STAGE_MAX_PARTS) fail(WX_ERR_INTERNAL, "partitioned GROUP BY: bad partition count");
-  const int64_t tile = gp_tile_rows();
-  const int64_t n_tiles = (t->n_rows + tile - 1) / tile;
-  // one 1024-thread tile workgroup per CU (two of 512); the plan scans G <= 1024
-  int64_t G = std::min<int64_t>(std::min<int64_t>((int64_t)d.cus * (1024 / WX_GP_TBLOCK), 1024), n_tiles);
-  const int64_t tpw = (n_tiles + G - 1) / G;
-  G = (n_tiles + tpw - 1) / tpw;
-  const int64_t target_items = 4ll * d.cus;
-  const int64_t work_cap = P + target_items + 2;
-  ensure(w, w.gp_mm, (size_t)G * 32, false);
-  ensure(w, w.gp_pcount, (size_t)G * P * 4, false);
-  ensure(w, w.gp_ptotal, (size_t)WX_GP_STAGE_MAX_PARTS * 8, false);
-  // cleared on every call (the plan also leaves it clean, but a call that
-  // failed between the tiles' adds and the plan would leave stale totals:
-  // ADVICE r4); P x 8 bytes
-  WX_HIP(hipMemsetAsync(w.gp_ptotal.p, 0, (size_t)P * 8, s));
-  ensure(w, w.gp_dir, (size_t)P * n_tiles * 4, false);
-  ensure(w, w.gp_vals, (size_t)n_tiles * tile * 4, false);
-  ensure(w, w.gp_bins, (size_t)n_tiles * tile * 2, false);
-  ensure(w, w.gp_work, (size_t)work_cap * 16, false);
-  ensure(w, w.gp_nwork, 8, false);
-  ensure(w, w.gp_pitem, (size_t)(P + 1) * 4, false);
-  ensure(w, w.gp_order, (size_t)(work_cap + 8) * 4, false);  // + 8: the XCD-dealt order's empty slots
-  if (work_cap > 4096) fail(WX_ERR_INTERNAL, "partitioned GROUP BY: more than 4096 work items");
-  ensure(w, w.gp_psum, (size_t)work_cap * B * 8, false);
-  ensure(w, w.gp_pcnt, (size_t)work_cap * B * 4, false);
-  ensure(w, w.gp_summary, 32, false);
-  ensure(w, w.gp_pnz, (size_t)P * 4, false);
-  ensure(w, w.g_ctrs, 64, true);
-  WxGroupPartArgs a{};
-  fill_cols(t, cols, a.col);
-  a.n_rows = t->n_rows;
-  a.n_tiles = n_tiles;
-  a.tiles_per_wg = (int)tpw;
-  a.n_wg = (int)G;
-  a.n_part = P;
-  a.key_lo = (int32_t)lo;
-  a.shift = shift;
-  a.mm = static_cast<wx_i64 *>(w.gp_mm.p);
-  a.pcount = static_cast<wx_u32 *>(w.gp_pcount.p);
-  a.ptotal = static_cast<wx_u64 *>(w.gp_ptotal.p);
-  a.dir = static_cast<wx_u32 *>(w.gp_dir.p);
-  a.vals = static_cast<float *>(w.gp_vals.p);
-  a.bins = static_cast<unsigned short *>(w.gp_bins.p);
-  a.work = static_cast<wx_i64 *>(w.gp_work.p);
-  a.n_work = static_cast<wx_i64 *>(w.gp_nwork.p);
-  a.pitem = static_cast<wx_u32 *>(w.gp_pitem.p);
-  a.order = static_cast<wx_u32 *>(w.gp_order.p);
-  a.work_cap = work_cap;
-  a.chunk = 1 << 16;
-  a.target_items = target_items;
-  a.psum = static_cast<double *>(w.gp_psum.p);
-  a.pcnt = static_cast<wx_u32 *>(w.gp_pcnt.p);
-  a.summary = static_cast<wx_i64 *>(w.gp_summary.p);
-  a.pnz = static_cast<wx_u32 *>(w.gp_pnz.p);
-  a.out_keys = d_keys;
-  a.out_sums = d_sums;
-  a.out_counts = reinterpret_cast<wx_i64 *>(d_counts);
-  a.capacity = capacity;
-  a.n_groups_out = reinterpret_cast<wx_i64 *>(ng);
-  a.ctrs = static_cast<wx_u64 *>(w.g_ctrs.p);
-  // the tile kernel's LDS: the staged tile (6 B per row) + 12 B per partition (+ its static words), within 160 KB
-  const int64_t tile_lds = tile * 6 + (int64_t)P * 12;
-  if (tile_lds + 1024 > 160 * 1024 / (1024 / WX_GP_TBLOCK))
-    fail(WX_ERR_INTERNAL, "partitioned GROUP BY: tile LDS exceeds the per-CU share");
-  // diagnostics only: per-phase times of the tile kernel (WX_GP_DIAG builds)
-  const bool diag = env_or("WARPDB_EXTRA_DEFINES", "").find("WX_GP_DIAG") != std::string::npos;
-  a.diag = nullptr;
-  if (diag) {
-    ensure(w, w.diag, (size_t)G * 16 * 8, false);
-    WX_HIP(hipMemsetAsync(w.diag.p, 0, (size_t)G * 16 * 8, s));
-    a.diag = static_cast<wx_u64 *>(w.diag.p);
-  }
-  launch(mod->fn("wx_group_part_tiles"), (unsigned)G, &a, s, timed, WX_GP_TBLOCK, (unsigned)tile_lds);
-  if (diag) {  // mean per-workgroup phase time per tile, 10 ns ticks -> us
-    std::vector<wx_u64> h((size_t)G * 16);
-    WX_HIP(hipMemcpyAsync(h.data(), w.diag.p, h.size() * 8, hipMemcpyDeviceToHost, s));
-    WX_HIP(hipStreamSynchronize(s));
-    const char *names[8] = {"write-out", "eval", "next-loads", "barrier1", "scan", "barrier2", "place", "barrier3"};
-    for (int role = 0; role < 2; ++role) {
-      std::fprintf(stderr, "[warpexec] tiles %s:", role ? "wave 15" : "wave 0 ");
-      double tot = 0;
-      for (int i = 0; i < 8; ++i) {
-        double m = 0;
-        for (int64_t b = 0; b < G; ++b) m += (double)h[(size_t)b * 16 + role * 8 + i];
-        m = m / (double)G / (double)tpw / 100.0;
-        tot += m;
-        std::fprintf(stderr, " %s %.2f", names[i], m);
-      }
-      std::fprintf(stderr, " | %.2f us per tile\n", tot);
-    }
-  }
-  launch(mod->fn("wx_group_part_plan"), 1, &a, s, timed, 1024);
-  // one workgroup per possible item; those past the plan's count return at once
-  launch(mod->fn("wx_group_part_agg"), (unsigned)((work_cap + 7) / 8 * 8), &a, s, timed, WX_GP_BLOCK,
-         (unsigned)(B * 12 + WX_GP_AGG_DIR_WORDS * 4));
-  launch(mod->fn("wx_group_part_count"), (unsigned)P, &a, s, timed, WX_GP_BLOCK);
-  launch(mod->fn("wx_group_part_scan2"), 1, &a, s, timed, 1024);
-  launch(mod->fn("wx_group_part_emit"), (unsigned)P, &a, s, timed, WX_GP_BLOCK);
-  int64_t h[4];
-  WX_HIP(hipMemcpyAsync(h, a.summary, sizeof h, hipMemcpyDeviceToHost, s));
-  WX_HIP(hipStreamSynchronize(s));
-  GpSummary r;
-  r.passing = h[0];
-  r.outside = h[1];
-  r.mn = h[2];
-  r.mx = h[3];
-  return r;
-}
-
-// memo of the last key range per (expressions, columns, rows): the next
-// call's first guess (never trusted for correctness: the window path's hash
-// and the partitioned pass's outside count both catch a stale range)
-uint64_t gp_memo_key(const Spec &spec, const wx_table *t, const std::vector<UsedCol> &cols) {
-  std::string k = spec.expr + '\x01' + spec.key + '\x01' + spec.cond + '\x01' + spec.custom + '\x01' +
-                  std::to_string(t->n_rows);
-  for (auto &c : cols) k += '\x01' + std::to_string(reinterpret_cast<uintptr_t>(t->cols[c.table_index].d_ptr));
-  return fnv1a(k);
-}
-
-void do_group_sum_rows(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond,
-                       const wx_launch &L, int32_t key_lo, int64_t capacity, int32_t *d_keys, double *d_sums,
-                       int64_t *d_counts, int64_t *d_n_groups, int64_t *h_n_groups, float *d_mins, float *d_maxs);
-void do_sort(void *d_a, float *d_v, int64_t count, int kind, int32_t ascending, const wx_launch *Lp, int64_t limit,
-             const void *src);
-
-// The GROUP module of a query (also the row-order GROUP BY's: its kernels
-// evaluate the same expressions).
-Spec group_spec(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond, const wx_launch &L,
-                bool minmax) {
-  Spec spec;
-  spec.op = WX_OP_GROUP;
-  spec.minmax = minmax ? 1 : 0;
-  spec.cols = used_columns(t, {val_expr, key_expr, cond});
-  spec.expr = one_line(val_expr);
-  spec.key = one_line(key_expr);
-  spec.cond = blank(cond) ? std::string() : one_line(cond);
-  spec.custom = read_custom(&L);
-  spec.extra = env_or("WARPDB_EXTRA_DEFINES", "");
-  spec.aligned = cols_aligned(t, spec.cols);
-  return spec;
-}
-
-void do_group_sum(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond,
-                  const wx_launch *Lp, int32_t key_lo, int64_t capacity, int32_t *d_keys, double *d_sums,
-                  int64_t *d_counts, int64_t *d_n_groups, int64_t *h_n_groups, float *d_mins = nullptr,
-                  float *d_maxs = nullptr, double *d_window = nullptr, int32_t n_slots = 0, int32_t slot_rank = 0,
-                  int32_t slot_groups = 0) {
-  const bool minmax = d_mins || d_maxs;
-  if (minmax && d_window) fail(WX_ERR_UNSUPPORTED, "GROUP BY partials carry SUM and COUNT only");
-  check_table(t);
-  const wx_launch L = Lp ? *Lp : default_launch();
-  if (L.flags & WX_F_ROW_ORDER) {
-    if (d_window) fail(WX_ERR_UNSUPPORTED, "row-order sums are not available for shard partials");
-    do_group_sum_rows(t, val_expr, key_expr, cond, L, key_lo, capacity, d_keys, d_sums, d_counts, d_n_groups,
-                      h_n_groups, d_mins, d_maxs);
-    return;
-  }
-  if (blank(val_expr) || blank(key_expr)) fail(WX_ERR_INVALID, "Empty query expression");
-  if (capacity < 0 || (capacity > 0 && (!d_keys || !d_sums || !d_counts)))
-    fail(WX_ERR_INVALID, "group outputs must hold `capacity` entries");
-  if ((int64_t)key_lo + WX_GROUP_WINDOW - 1 > INT32_MAX) fail(WX_ERR_INVALID, "key window out of range");
-  const Spec spec = group_spec(t, val_expr, key_expr, cond, L, minmax);
-  const int gblock = gp_gblock();
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  auto mod = get_module(L.device, spec, true);
-  DeviceState &d = device_state(L.device, true);
-  Workspace &w = workspace(L.device, s);
-  OpLock op_lock(w.op_mu);
-  // the general-key table must hold every distinct key outside the window
-  const uint32_t hcap = next_pow2(std::max<int64_t>(4096, 2 * capacity));
-  if (w.g_hcap < hcap) {
-    ensure(w, w.g_tag, (size_t)hcap * 8, true);
-    ensure(w, w.g_sum, (size_t)hcap * 8, true);
-    ensure(w, w.g_cnt, (size_t)hcap * 8, true);
-    ensure(w, w.g_used, (size_t)hcap * 4, true);
-    WX_HIP(hipMemsetAsync(w.g_tag.p, 0, w.g_tag.bytes, s));
-    WX_HIP(hipMemsetAsync(w.g_sum.p, 0, w.g_sum.bytes, s));
-    WX_HIP(hipMemsetAsync(w.g_cnt.p, 0, w.g_cnt.bytes, s));
-    w.g_hcap = hcap;
-  }
-  ensure(w, w.g_win_sum, WX_GROUP_WINDOW * 8, true);
-  ensure(w, w.g_win_cnt, WX_GROUP_WINDOW * 8, true);
-  if (minmax && w.g_mm_cap < w.g_hcap) {
-    ensure(w, w.g_win_min, WX_GROUP_WINDOW * 4, false);
-    ensure(w, w.g_win_max, WX_GROUP_WINDOW * 4, true);
-    ensure(w, w.g_min, (size_t)w.g_hcap * 4, false);
-    ensure(w, w.g_max, (size_t)w.g_hcap * 4, false);
-    WX_HIP(hipMemsetAsync(w.g_win_min.p, 0xff, w.g_win_min.bytes, s));
-    WX_HIP(hipMemsetAsync(w.g_min.p, 0xff, w.g_min.bytes, s));
-    WX_HIP(hipMemsetAsync(w.g_max.p, 0, w.g_max.bytes, s));
-    w.g_mm_cap = w.g_hcap;
-  }
-  ensure(w, w.g_ctrs, 64, true);
-  int64_t *ng = d_n_groups;
-  if (!ng) {
-    ensure(w, w.g_ngroups, 8, false);
-    ng = static_cast<int64_t *>(w.g_ngroups.p);
-  }
-  const bool timed = (L.flags & WX_F_TIME) != 0;
-  if (capacity > WX_GROUP_HSORT_MAX && !minmax && !d_window && t->n_rows >= gp_min_rows() && t->n_rows > 0 &&
-      env_or("WARPDB_GROUP_PARTITION", "1") != "0") {
-    // the key range: the memo of the previous call, else a sample (widened),
-    // else an exact pass (see gp_min_rows above)
-    const uint64_t mkey = gp_memo_key(spec, t, spec.cols);
-    if (w.gp_memo.size() > 256) w.gp_memo.clear();
-    KeyRange r;
-    bool from_memo = false;
-    auto it = w.gp_memo.find(mkey);
-    // a window-kind memo is re-checked every 16th call (nothing else would
-    // notice a table rewritten in place with many more keys)
-    if (it != w.gp_memo.end() && (!it->second.window || it->second.uses < 16)) {
-      r.any = true;
-      r.lo = it->second.lo;
-      r.hi = it->second.hi;
-      ++it->second.uses;
-      from_memo = true;
-    } else {
-      if (env_or("WARPDB_GP_GUESS", "1") != "0") {
-        r = sample_keys(t, spec.cols, mod.get(), w, s, timed);
-        if (r.any) {
-          const int64_t margin = std::max<int64_t>(r.span() / 8, 64);
-          r.lo = std::max<int64_t>(INT32_MIN, r.lo - margin);
-          r.hi = std::min<int64_t>(INT32_MAX, r.hi + margin);
-        }
-      }
-      if (!r.any || r.span() > gp_max_span()) r = probe_keys(t, spec.cols, mod.get(), d, w, s, timed);
-    }
-    if (r.any && r.span() > WX_GROUP_WINDOW && r.span() <= gp_max_span()) {
-      GpSummary g = group_partitioned(t, spec.cols, mod.get(), d, w, s, timed, r.lo, r.span(), capacity, d_keys,
-                                      d_sums, d_counts, ng);
-      bool done = g.outside == 0;
-      if (!done && g.mx - g.mn + 1 > WX_GROUP_WINDOW && g.mx - g.mn + 1 <= gp_max_span()) {
-        // some key was outside the planned range: again over the exact one
-        g = group_partitioned(t, spec.cols, mod.get(), d, w, s, timed, g.mn, g.mx - g.mn + 1, capacity, d_keys,
-                              d_sums, d_counts, ng);
-        if (g.outside) fail(WX_ERR_INTERNAL, "partitioned GROUP BY: rows outside the exact key range");
-        done = true;
-      }
-      if (g.passing) {
-        Workspace::GpMemo m;
-        m.lo = g.mn;
-        m.hi = g.mx;
-        m.window = g.mx - g.mn + 1 <= WX_GROUP_WINDOW;
-        w.gp_memo[mkey] = m;
-      } else {
-        w.gp_memo.erase(mkey);
-      }
-      if (done) {
-        if (h_n_groups) WX_HIP(hipMemcpy(h_n_groups, ng, 8, hipMemcpyDeviceToHost));
-        if ((L.flags & WX_F_SYNC) || h_n_groups) check_errors(w);
-        return;
-      }
-      // the exact range fits the window (or is too wide): the window path below
-      r.any = true;
-      r.lo = g.mn;
-      r.hi = g.mx;
-    }
-    if (r.any && r.span() <= WX_GROUP_WINDOW) {  // every (sampled) key inside the window: move it there
-      key_lo = (int32_t)std::min<int64_t>(r.lo, INT32_MAX - (WX_GROUP_WINDOW - 1));
-      if (!from_memo) w.gp_memo[mkey] = Workspace::GpMemo{r.lo, r.hi, true, 0};
-    }
-  }
-  WxGroupArgs a;
-  fill_cols(t, spec.cols, a.col);
-  a.n_rows = t->n_rows;
-  a.win_sum = static_cast<double *>(w.g_win_sum.p);
-  a.win_cnt = static_cast<wx_u64 *>(w.g_win_cnt.p);
-  a.h_tag = static_cast<wx_u64 *>(w.g_tag.p);
-  a.h_sum = static_cast<double *>(w.g_sum.p);
-  a.h_cnt = static_cast<wx_u64 *>(w.g_cnt.p);
-  a.h_used = static_cast<wx_u32 *>(w.g_used.p);
-  a.ctrs = static_cast<wx_u64 *>(w.g_ctrs.p);
-  a.win_min = static_cast<wx_u32 *>(w.g_win_min.p);
-  a.win_max = static_cast<wx_u32 *>(w.g_win_max.p);
-  a.h_min = static_cast<wx_u32 *>(w.g_min.p);
-  a.h_max = static_cast<wx_u32 *>(w.g_max.p);
-  a.hmask = w.g_hcap - 1;
-  a.key_lo = key_lo;
-  // The finalize: its own one-workgroup launch after the (possible) key
-  // sort (fusing it into wx_group_sum's last workgroup measured slower,
-  // DESIGN.md 5.2).
-  WxGroupFinArgs f;
-  f.sorted = nullptr;
-  f.win_sum = a.win_sum;
-  f.win_cnt = a.win_cnt;
-  f.h_tag = a.h_tag;
-  f.h_sum = a.h_sum;
-  f.h_cnt = a.h_cnt;
-  f.h_used = a.h_used;
-  f.ctrs = a.ctrs;
-  f.win_min = a.win_min;
-  f.win_max = a.win_max;
-  f.h_min = a.h_min;
-  f.h_max = a.h_max;
-  f.out_keys = d_keys;
-  f.out_sums = d_sums;
-  f.out_counts = reinterpret_cast<wx_i64 *>(d_counts);
-  f.out_mins = d_mins;
-  f.out_maxs = d_maxs;
-  f.n_groups_out = reinterpret_cast<wx_i64 *>(ng);
-  f.capacity = capacity;
-  f.key_lo = key_lo;
-  f.win_out = d_window;
-  f.slots = (d_window && n_slots > 0) ? d_window + WX_GROUP_EXCHANGE : nullptr;
-  f.n_slots = n_slots;
-  f.slot_rank = slot_rank;
-  f.slot_groups = slot_groups;
-  if (t->n_rows > 0) {
-    const int gpc = grid_per_cu(4 * WX_BLOCK / gblock);  // 16 waves per CU
-    const unsigned grid = grid_for(((t->n_rows + 3) / 4 + gblock / WX_BLOCK - 1) / (gblock / WX_BLOCK), d.cus, gpc);
-    launch(mod->fn("wx_group_sum"), grid, &a, s, (L.flags & WX_F_TIME) != 0, (unsigned)gblock);
-  }
-  // More than WX_GROUP_HSORT_MAX general keys (possible only when the caller
-  // allows that many groups): sort them on the device for the finalize.
-  const wx_u64 *sorted = nullptr;
-  if (capacity > WX_GROUP_HSORT_MAX && t->n_rows > 0) {
-    int64_t nh = 0;
-    WX_HIP(hipMemcpyAsync(&nh, a.ctrs, 8, hipMemcpyDeviceToHost, s));
-    WX_HIP(hipStreamSynchronize(s));
-    if (nh > WX_GROUP_HSORT_MAX) {
-      int64_t npad = WX_SORT_LDS;
-      while (npad < nh) npad <<= 1;
-      ensure(w, w.g_sorted, (size_t)npad * 8, false);
-      WxGroupGatherArgs ga;
-      ga.ctrs = a.ctrs;
-      ga.h_used = a.h_used;
-      ga.h_tag = a.h_tag;
-      ga.keys = static_cast<wx_u64 *>(w.g_sorted.p);
-      ga.npad = npad;
-      launch(mod->fn("wx_group_gather"), grid_for(npad, d.cus, 8), &ga, s);
-      bitonic_u64(L.device, ga.keys, npad, s);
-      sorted = ga.keys;
-    }
-  }
-  f.sorted = sorted;
-  void *params[] = {&f};
-  WX_HIP(hipModuleLaunchKernel(mod->fn("wx_group_finalize"), 1, 1, 1, 1024, 1, 1, 0, s, params, nullptr));  // WX_GFIN_BLOCK
-  if (h_n_groups) {  // read before the error check: a capacity error still reports the count
-    WX_HIP(hipStreamSynchronize(s));
-    WX_HIP(hipMemcpy(h_n_groups, ng, 8, hipMemcpyDeviceToHost));
-  }
-  if ((L.flags & WX_F_SYNC) || h_n_groups) check_errors(w);
-}
-
-std::string rs_rank_extra(const std::string &arch);
-
-// Row-order GROUP BY when the groups' keys span at most 2048 values
-// (wx_group_rows.hip): per-range bin counts straight from the table, their
-// totals / bases / per-range offsets, one stable counting scatter of the
-// passing rows' values into key-major row-ordered segments, one wave per
-// group folding its segment.  No compaction, no key bits, no radix pass.
-// Groups of more than WX_XF_BIG rows are folded in WX_XF_CHUNK-value chunks
-// by wx_xf_big_* (wx_util.hip) instead of one wave each; launches them and
-// returns the count the per-group fold skips above (0: no such group).  The
-// groups' segments follow each other in group order (key-major values).
-int64_t xf_big_groups(Module *umod, const float *svals, const int64_t *d_counts, int64_t ng, int64_t passing,
-                      double *d_sums, Workspace &w, hipStream_t s, bool timed) {
-  // $WARPDB_XF_BIG: "0" off, unset / "1" the default threshold, else the
-  // threshold in rows (at least one chunk)
-  const std::string xb = env_or("WARPDB_XF_BIG", "1");
-  if (xb == "0") return 0;
-  const int64_t big = xb == "1" ? (int64_t)WX_XF_BIG : std::max<int64_t>(std::atoll(xb.c_str()), WX_XF_CHUNK);
-  if (passing <= big || ng < 1 || ng > (1 << 20)) return 0;
-  std::vector<int64_t> hc((size_t)ng);
-  WX_HIP(hipMemcpyAsync(hc.data(), d_counts, (size_t)ng * 8, hipMemcpyDeviceToHost, s));
-  WX_HIP(hipStreamSynchronize(s));
-  w.xf_host.clear();
-  int64_t start = 0, chunks = 0;
-  for (int64_t g = 0; g < ng; ++g) {
-    if (hc[g] > big) {
-      w.xf_host.insert(w.xf_host.end(), {g, start, hc[g], chunks});
-      chunks += (hc[g] + WX_XF_CHUNK - 1) / WX_XF_CHUNK;
-    }
-    start += hc[g];
-  }
-  if (w.xf_host.empty()) return 0;
-  const int n_ent = (int)(w.xf_host.size() / 4);
-  ensure(w, w.xf_ent, w.xf_host.size() * 8, false);
-  ensure(w, w.xf_approx, (size_t)chunks * 8, false);
-  ensure(w, w.xf_rec, (size_t)chunks * 64, false);
-  WX_HIP(hipMemcpyAsync(w.xf_ent.p, w.xf_host.data(), w.xf_host.size() * 8, hipMemcpyHostToDevice, s));
-  WxXfBigArgs x{};
-  x.svals = svals;
-  x.ent = static_cast<const wx_i64 *>(w.xf_ent.p);
-  x.n_ent = n_ent;
-  x.n_chunks = chunks;
-  x.approx = static_cast<double *>(w.xf_approx.p);
-  x.rec = static_cast<double *>(w.xf_rec.p);
-  x.out_sums = d_sums;
-  const unsigned cg = (unsigned)std::min<int64_t>(chunks, 4096);
-  launch(umod->fn("wx_xf_big_approx"), cg, &x, s, timed, 64);
-  launch(umod->fn("wx_xf_big_exact"), cg, &x, s, timed, 64);
-  launch(umod->fn("wx_xf_big_combine"), (unsigned)n_ent, &x, s, timed, 64);
-  return big;
-}
-
-// The span path's tail, once the bins' totals are in ro_tot and their
-// exclusive prefix in ro_tot + 2048: each range's first slot of every bin,
-// the stable counting scatter of the passing values into key-major order,
-// and the exact row-order fold of every group's segment.
-void ro_scatter_fold(Module *gmod, Module *umod, WxRoArgs &a, int64_t passing, const int64_t *d_counts, int64_t ng,
-                     double *d_sums, Workspace &w, hipStream_t s, bool timed) {
-  if (passing > 0xffffffffll)  // counts, offsets and scatter positions are 32-bit
-    fail(WX_ERR_UNSUPPORTED, "row-order sums over a key span take at most 2^32 - 1 passing rows");
-  // the key-major copy (4 B per passing row) stays in the workspace, as the
-  // radix sort's ping-pong buffer does (a 4 GB hipMalloc per query cost ms)
-  ensure(w, w.ro_vals, (size_t)std::max<int64_t>(1, passing) * 4, false);
-  a.out = static_cast<float *>(w.ro_vals.p);
-  WxRoScanArgs sc{};
-  sc.cnt = a.cnt;
-  sc.ranges = a.ranges;
-  sc.base = static_cast<wx_u32 *>(w.ro_tot.p) + 2048;
-  sc.off = static_cast<wx_u32 *>(w.ro_off.p);
-  launch(umod->fn("wx_ro_scan"), 32, &sc, s, timed, 256);
-  launch(gmod->fn("wx_ro_scatter"), (unsigned)a.ranges, &a, s, timed, WX_RO_THREADS);
-  WxRoFoldArgs f{};
-  f.svals = a.out;
-  f.gcounts = reinterpret_cast<const wx_i64 *>(d_counts);
-  f.n_groups = ng;
-  f.out_sums = d_sums;
-  f.skip_above = xf_big_groups(umod, a.out, d_counts, ng, passing, d_sums, w, s, timed);
-  launch(umod->fn("wx_ro_fold"), (unsigned)std::min<int64_t>(ng, 1 << 20), &f, s, timed, 64);
-}
-
-// count arguments of the span path over [kmin, kmin + span)
-WxRoArgs ro_args(const wx_table *t, const Spec &spec, DeviceState &d, int32_t kmin, int span, Workspace &w) {
-  const int64_t n = t->n_rows;
-  const int64_t tiles = (n + WX_RO_TILE_ROWS - 1) / WX_RO_TILE_ROWS;
-  // two 512-thread workgroups per CU (72 KB of LDS each), one range each:
-  // one workgroup per CU (LDS-padded) 13.6 vs 12.4 ms per query,
-  // nontemporal value stores 15.4, 16 384-row tiles at one workgroup per CU
-  // 12.9 vs 12.9 (their runs halve the written bytes, 7.56 -> 5.76 GB, and
-  // the time stays; profiles/r05/ro_scatter_ab.txt)
-  const int ranges = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, 2ll * d.cus));
-  ensure(w, w.ro_cnt, (size_t)ranges * 2048 * 4, false);
-  ensure(w, w.ro_off, (size_t)ranges * 2048 * 4, false);
-  ensure(w, w.ro_tot, 2 * 2048 * 4, false);
-  ensure(w, w.g_ctrs, 64, true);
-  WxRoArgs a{};
-  fill_cols(t, spec.cols, a.col);
-  a.n_rows = n;
-  a.key_lo = kmin;
-  a.span = span;
-  a.ranges = ranges;
-  a.cnt = static_cast<wx_u32 *>(w.ro_cnt.p);
-  a.off = static_cast<const wx_u32 *>(w.ro_off.p);
-  a.ctrs = static_cast<wx_u64 *>(w.g_ctrs.p);
-  a.info = nullptr;
-  return a;
-}
-
-// Row-order GROUP BY when the groups' keys span at most 2048 values
-// (wx_group_rows.hip), after an ordinary call gave the groups and counts:
-// per-range bin counts straight from the table, their totals / bases (checked
-// against the ordinary call) / per-range offsets, one stable counting scatter
-// of the passing rows' values into key-major row-ordered segments, the exact
-// fold of each group's segment.  No compaction, no key bits, no radix pass.
-void group_rows_span(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond,
-                     const wx_launch &L, int32_t kmin, int span, const int32_t *d_keys, double *d_sums,
-                     const int64_t *d_counts, int64_t ng, Workspace &w, hipStream_t s, bool minmax) {
-  const Spec spec = group_spec(t, val_expr, key_expr, cond, L, minmax);
-  auto gmod = get_module(L.device, spec, true);
-  auto umod = util_module(L.device, true);
-  DeviceState &d = device_state(L.device, true);
-  const bool timed = (L.flags & WX_F_TIME) != 0;
-  int64_t passing = 0;  // the groups' rows: the key-major array's length
-  {
-    std::vector<int64_t> hc((size_t)ng);
-    WX_HIP(hipMemcpyAsync(hc.data(), d_counts, (size_t)ng * 8, hipMemcpyDeviceToHost, s));
-    WX_HIP(hipStreamSynchronize(s));
-    for (int64_t c : hc) passing += c;
-  }
-  if (passing > 0xffffffffll)
-    fail(WX_ERR_UNSUPPORTED, "row-order sums over a key span take at most 2^32 - 1 passing rows");
-  WxRoArgs a = ro_args(t, spec, d, kmin, span, w);
-  wx_u32 *tot = static_cast<wx_u32 *>(w.ro_tot.p);
-  launch(gmod->fn("wx_ro_count"), (unsigned)a.ranges, &a, s, timed, WX_RO_THREADS);
-  WxRoScanArgs sc{};
-  sc.cnt = a.cnt;
-  sc.totals = tot;
-  sc.ranges = a.ranges;
-  launch(umod->fn("wx_ro_scan"), 32, &sc, s, timed, 256);
-  WxRoBaseArgs b{};
-  b.totals = tot;
-  b.base = tot + 2048;
-  b.gkeys = d_keys;
-  b.gcounts = reinterpret_cast<const wx_i64 *>(d_counts);
-  b.n_groups = ng;
-  b.key_lo = kmin;
-  b.ctrs = a.ctrs;
-  launch(umod->fn("wx_ro_base"), 1, &b, s, timed, 1024);
-  ro_scatter_fold(gmod.get(), umod.get(), a, passing, d_counts, ng, d_sums, w, s, timed);
-  check_errors(w);
-}
-
-// The span path without the ordinary call (no MIN / MAX asked): a key range
-// from the memo of an earlier call or a strided sample picks a 2048-key span
-// around it, and the groups come straight from the bins' totals (the keys of
-// the non-empty bins, ascending, and their counts).  Returns false, having
-// written nothing the caller keeps, when the sample was too wide or a row's
-// key fell outside the span (the count kernel flags it): the caller then runs
-// the ordinary call first (and does for the next 16 calls over the same
-// expressions and table, so a sample that keeps missing costs once per 17).
-// 1: done; 0: the ordinary call first (a recent miss, no sampled row, or a
-// key outside the guessed span); 2: the keys span more than 2048 (the
-// sample or the memo says so), the general path without the ordinary call
-int group_rows_direct(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond,
-                       const wx_launch &L, int64_t capacity, int32_t *d_keys, double *d_sums, int64_t *d_counts,
-                       int64_t *d_n_groups, int64_t *h_n_groups, Workspace &w, hipStream_t s) {
-  const Spec spec = group_spec(t, val_expr, key_expr, cond, L, false);
-  auto gmod = get_module(L.device, spec, true);
-  auto umod = util_module(L.device, true);
-  DeviceState &d = device_state(L.device, true);
-  const bool timed = (L.flags & WX_F_TIME) != 0;
-  const uint64_t mkey = gp_memo_key(spec, t, spec.cols);
-  auto miss = w.ro_miss.find(mkey);
-  if (miss != w.ro_miss.end() && miss->second-- > 0) return 0;  // missed lately: the ordinary call first
-  if (miss != w.ro_miss.end()) w.ro_miss.erase(miss);
-  KeyRange r;
-  auto it = w.gp_memo.find(mkey);
-  if (it != w.gp_memo.end()) {
-    r.any = true;
-    r.lo = it->second.lo;
-    r.hi = it->second.hi;
-  } else {
-    r = sample_keys(t, spec.cols, gmod.get(), w, s, timed);
-  }
-  if (!r.any) return 0;
-  if (r.span() > 2048) return 2;
-  // the sampled keys centred in the span, inside the int32 range
-  int64_t lo = r.lo - (2048 - r.span()) / 2;
-  lo = std::max<int64_t>(INT32_MIN, std::min<int64_t>(lo, (int64_t)INT32_MAX - 2047));
-  WxRoArgs a = ro_args(t, spec, d, (int32_t)lo, 2048, w);
-  ensure(w, w.ro_info, 64, false);
-  WX_HIP(hipMemsetAsync(w.ro_info.p, 0, 64, s));
-  a.info = static_cast<wx_i64 *>(w.ro_info.p);
-  wx_u32 *tot = static_cast<wx_u32 *>(w.ro_tot.p);
-  launch(gmod->fn("wx_ro_count"), (unsigned)a.ranges, &a, s, timed, WX_RO_THREADS);
-  WxRoScanArgs sc{};
-  sc.cnt = a.cnt;
-  sc.totals = tot;
-  sc.ranges = a.ranges;
-  launch(umod->fn("wx_ro_scan"), 32, &sc, s, timed, 256);
-  WxRoBaseArgs b{};
-  b.totals = tot;
-  b.base = tot + 2048;
-  b.key_lo = (int32_t)lo;
-  b.ctrs = a.ctrs;
-  b.out_keys = d_keys;
-  b.out_counts = reinterpret_cast<wx_i64 *>(d_counts);
-  b.capacity = capacity;
-  b.n_groups_out = reinterpret_cast<wx_i64 *>(d_n_groups);
-  b.info = a.info;
-  launch(umod->fn("wx_ro_base"), 1, &b, s, timed, 1024);
-  int64_t info[5];
-  WX_HIP(hipMemcpyAsync(info, w.ro_info.p, sizeof(info), hipMemcpyDeviceToHost, s));
-  WX_HIP(hipStreamSynchronize(s));
-  if (info[2]) {  // a key outside the guessed span: the ordinary call first, for the next 16 calls too
-    w.gp_memo.erase(mkey);
-    if (w.ro_miss.size() > 256) w.ro_miss.clear();
-    w.ro_miss[mkey] = 16;
-    return 0;
-  }
-  const int64_t ng = info[0];
-  if (h_n_groups) *h_n_groups = ng;
-  if (ng > 0) {
-    if (w.gp_memo.size() > 256) w.gp_memo.clear();  // bounded, as the ordinary path's
-    w.gp_memo[mkey] = Workspace::GpMemo{info[3], info[4], info[4] - info[3] + 1 <= WX_GROUP_WINDOW, 0};
-  }
-  if (ng > capacity) {
-    check_errors(w);  // the base kernel raised the capacity bit: the ordinary call's error
-    fail(WX_ERR_CAPACITY, "group table / output capacity exceeded");
-  }
-  if (ng > 0) ro_scatter_fold(gmod.get(), umod.get(), a, info[1], d_counts, ng, d_sums, w, s, timed);
-  check_errors(w);
-  return 1;
-}
-
-// The column an expression reads when it is nothing but `name[idx]` (outer
-// parentheses and blanks allowed), else null.
-const wx_col *bare_column(const wx_table *t, const char *expr) {
-  if (!t || !expr) return nullptr;
-  std::string e(expr);
-  auto trim = [&e]() {
-    const size_t b = e.find_first_not_of(" \t\n\r"), x = e.find_last_not_of(" \t\n\r");
-    e = b == std::string::npos ? std::string() : e.substr(b, x - b + 1);
-  };
-  trim();
-  while (e.size() >= 2 && e.front() == '(' && e.back() == ')') {
-    int depth = 0;
-    bool outer = true;  // the first '(' closes at the last character
-    for (size_t i = 0; i + 1 < e.size(); ++i) {
-      depth += e[i] == '(' ? 1 : e[i] == ')' ? -1 : 0;
-      if (depth == 0) {
-        outer = false;
-        break;
-      }
-    }
-    if (!outer) break;
-    e = e.substr(1, e.size() - 2);
-    trim();
-  }
-  const std::string tail = "[idx]";
-  if (e.size() <= tail.size() || e.compare(e.size() - tail.size(), tail.size(), tail) != 0) return nullptr;
-  const std::string name = e.substr(0, e.size() - tail.size());
-  for (int c = 0; c < t->n_cols; ++c)
-    if (t->cols[c].name && name == t->cols[c].name) return &t->cols[c];
-  return nullptr;
-}
-
-// the LSD radix sort (below); with res_k the sorted keys and payload are
-// left wherever the last pass wrote them (*res_k / *res_v) instead of being
-// copied back into d_a / d_v
-void radix_sort(void *d_a, float *d_v, int64_t count, int kind, int32_t ascending, const wx_launch &L, Workspace &w,
-                hipStream_t s, int64_t limit = -1, const void *src0 = nullptr, void **res_k = nullptr,
-                float **res_v = nullptr, const float *src_v = nullptr);
-
-// The general row-order path: (1) the passing rows' values and key bits in
-// row order (ordered compactions; a bare int32 key column with no WHERE is
-// read in place), (2) the stable radix pair sort by key, (3) each group's
-// first row -- from the ordinary call's counts (ng >= 0: d_keys / d_counts
-// hold its ng groups) or, with no ordinary call (ng < 0), by run-length
-// encoding the sorted keys into d_keys / d_counts / d_n_groups -- (4) each
-// group's values folded in row order.
-void group_rows_general(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond,
-                        const wx_launch &L, const wx_launch &L1, int64_t capacity, int32_t *d_keys, double *d_sums,
-                        int64_t *d_counts, int64_t *d_n_groups, int64_t &ng, Workspace &w, hipStream_t s) {
-  const int64_t n = t->n_rows;
-  if (n > 0xffffffffll) fail(WX_ERR_UNSUPPORTED, "row-order sums sort at most 2^32 - 1 rows");
-  ensure(w, w.ro_vals, (size_t)n * 4, false);
-  ensure(w, w.ro_keys, (size_t)n * 4, false);
-  float *vals = static_cast<float *>(w.ro_vals.p);
-  int32_t *keys = static_cast<int32_t *>(w.ro_keys.p);
-  int64_t m = 0, mk = 0;
-  // a bare float32 value column and no WHERE: the sort's first pass reads
-  // the column itself as its payload, no value projection
-  const wx_col *vc = blank(cond) ? bare_column(t, val_expr) : nullptr;
-  if (vc && (vc->dtype != WX_FLOAT32 || !vc->d_ptr)) vc = nullptr;
-  if (vc)
-    m = t->n_rows;
-  else
-    do_project_filter(t, val_expr, cond, &L1, WX_MODE_COMPACT, vals, nullptr, 8, 0, nullptr, &m);
-  // a bare int32 key column and no WHERE: the sort's first pass reads the
-  // column itself (its bits are the keys), no key projection
-  const wx_col *kc = blank(cond) ? bare_column(t, key_expr) : nullptr;
-  if (kc && (kc->dtype != WX_INT32 || !kc->d_ptr)) kc = nullptr;
-  if (kc) {
-    mk = t->n_rows;
-  } else {
-    // the key's bits through the float-valued compaction, unchanged
-    const std::string kx = "__int_as_float((int)(" + std::string(key_expr) + "))";
-    do_project_filter(t, kx.c_str(), cond, &L1, WX_MODE_COMPACT, reinterpret_cast<float *>(keys), nullptr, 8, 0,
-                      nullptr, &mk);
-  }
-  if (m != mk) fail(WX_ERR_INTERNAL, "row-order GROUP BY: value and key compactions disagree");
-  // stable: row order kept within a key; the fold reads the sorted arrays
-  // where the last pass left them (no copy back)
-  const void *ksrc = kc ? kc->d_ptr : nullptr;
-  const float *vsrc = vc ? static_cast<const float *>(vc->d_ptr) : nullptr;
-  const int32_t *sk = kc ? static_cast<const int32_t *>(ksrc) : keys;
-  const float *sv = vc ? vsrc : vals;
-  if (m > 1) {
-    if (env_or("WARPDB_SORT", "radix") == "bitonic") {
-      if (vc) WX_HIP(hipMemcpyAsync(vals, vsrc, (size_t)m * 4, hipMemcpyDeviceToDevice, s));
-      do_sort(keys, vals, m, 1, 1, &L1, -1, ksrc);
-      sk = keys;
-      sv = vals;
-    } else {
-      void *rk = nullptr;
-      float *rv = nullptr;
-      radix_sort(keys, vals, m, 1, 1, L1, w, s, -1, ksrc, &rk, &rv, vsrc);
-      sk = static_cast<const int32_t *>(rk);
-      sv = rv;
-    }
-  }
-  const bool timed = (L.flags & WX_F_TIME) != 0;
-  WxGroupFoldArgs a{};
-  a.skeys = sk;
-  a.svals = sv;
-  a.m = m;
-  a.gkeys = d_keys;
-  a.gcounts = reinterpret_cast<const wx_i64 *>(d_counts);
-  a.n_groups = ng;
-  a.out_sums = d_sums;
-  ensure(w, w.g_ctrs, 64, true);
-  a.ctrs = static_cast<wx_u64 *>(w.g_ctrs.p);
-  auto mod = util_module(L.device, true);
-  if (ng < 0) {
-    // no ordinary call ran: the groups are the sorted keys' runs, in
-    // ascending key order -- keys, counts and first rows by run-length
-    // encoding (the counts then cover the rows by construction)
-    // wave ranges: at most 32 768, each a multiple of 64 rows
-    const int n_blk = (int)std::min<int64_t>(32768, std::max<int64_t>(1, (m + 16383) / 16384));
-    ensure(w, w.gf_chunks, 64 + (size_t)n_blk * 8, false);
-    WxRleArgs r{};
-    r.sk = sk;
-    r.m = m;
-    r.n_blk = n_blk;
-    r.span = ((m + n_blk - 1) / n_blk + 63) / 64 * 64;
-    const unsigned rle_grid = (unsigned)((n_blk + WX_RLE_BLOCK / 64 - 1) / (WX_RLE_BLOCK / 64));
-    r.n_out = static_cast<wx_i64 *>(w.gf_chunks.p);
-    r.blk = r.n_out + 8;
-    r.n_groups_out = reinterpret_cast<wx_i64 *>(d_n_groups);
-    r.capacity = capacity;
-    r.out_keys = d_keys;
-    r.out_counts = reinterpret_cast<wx_i64 *>(d_counts);
-    launch(mod->fn("wx_rle_count"), rle_grid, &r, s, timed, WX_RLE_BLOCK);
-    launch(mod->fn("wx_rle_scan"), 1u, &r, s, timed, WX_RLE_BLOCK);
-    WX_HIP(hipMemcpyAsync(&w.host_word, r.n_out, 8, hipMemcpyDeviceToHost, s));
-    WX_HIP(hipStreamSynchronize(s));
-    ng = (int64_t)w.host_word;
-    if (ng > capacity) fail(WX_ERR_CAPACITY, "group table / output capacity exceeded");
-    ensure(w, w.gf_starts, (size_t)std::max<int64_t>(ng, 1) * 8, false);
-    r.starts = static_cast<wx_i64 *>(w.gf_starts.p);
-    if (ng > 0) {
-      launch(mod->fn("wx_rle_emit"), rle_grid, &r, s, timed, WX_RLE_BLOCK);
-      launch(mod->fn("wx_rle_counts"), (unsigned)((ng + WX_GS_BLOCK - 1) / WX_GS_BLOCK), &r, s, timed, WX_GS_BLOCK);
-    }
-    a.n_groups = ng;
-    a.starts = r.starts;
-  } else {
-    // each group's first sorted row: the counts' exclusive prefix (the
-    // groups come in ascending key order and the sorted array holds
-    // exactly their rows, which wx_group_starts_scan checks)
-    const int64_t n_chunks = (ng + WX_GS_CHUNK - 1) / WX_GS_CHUNK;
-    ensure(w, w.gf_starts, (size_t)ng * 8, false);
-    ensure(w, w.gf_chunks, (size_t)n_chunks * 8, false);
-    a.starts = static_cast<wx_i64 *>(w.gf_starts.p);
-    a.chunk_sums = static_cast<wx_i64 *>(w.gf_chunks.p);
-    a.n_chunks = n_chunks;
-    launch(mod->fn("wx_group_starts_sum"), (unsigned)n_chunks, &a, s, timed, WX_GS_BLOCK);
-    launch(mod->fn("wx_group_starts_scan"), 1u, &a, s, timed, 1024);
-    launch(mod->fn("wx_group_starts_emit"), (unsigned)n_chunks, &a, s, timed, WX_GS_BLOCK);
-  }
-  if (ng > 0) {
-    ensure(w, w.gf_big, 64 + (size_t)ng * 8, false);
-    a.big_n = static_cast<wx_u32 *>(w.gf_big.p);
-    a.big_list = reinterpret_cast<wx_i64 *>(static_cast<char *>(w.gf_big.p) + 64);
-    // $WARPDB_FOLD_SMALL: the largest group folded by one lane (0: every group one wave, for A/B)
-    const std::string fs = env_or("WARPDB_FOLD_SMALL", "");
-    a.small_max = fs.empty() ? (int64_t)WX_FOLD_SMALL : std::max<int64_t>(0, std::atoll(fs.c_str()));
-    WX_HIP(hipMemsetAsync(a.big_n, 0, 4, s));
-    a.skip_above = xf_big_groups(mod.get(), sv, d_counts, ng, m, d_sums, w, s, timed);
-    launch(mod->fn("wx_group_fold_small"), (unsigned)((ng + WX_GS_BLOCK - 1) / WX_GS_BLOCK), &a, s, timed,
-           WX_GS_BLOCK);
-    launch(mod->fn("wx_group_fold"), (unsigned)std::min<int64_t>(ng, 4096), &a, s, timed, 64);
-  }
-  WX_HIP(hipStreamSynchronize(s));
-  // (the sorted arrays -- ro_vals / ro_keys and the sort's ping-pong
-  // buffers -- stay in the workspace for the next call, as the span path's do)
-  check_errors(w);
-}
-
-// GROUP BY with each group's sum folded in ascending row order, one double
-// add per row (WX_F_ROW_ORDER): the reference's std::map fold
-// (src/warpdb.cpp:373-385) to the bit, the same on every run.  Keys spanning
-// at most 2048: the key-span path (counting scatter + fold,
-// wx_group_rows.hip), straight from the table or after the ordinary call.
-// Wider: the general path (group_rows_general: compactions, stable radix
-// pair sort, fold), its groups from the ordinary call or, with no MIN / MAX
-// asked, from the sorted keys' runs.  MIN / MAX always come from the
-// ordinary call (they do not depend on order).  Synchronous.
-void do_group_sum_rows(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond,
-                       const wx_launch &L, int32_t key_lo, int64_t capacity, int32_t *d_keys, double *d_sums,
-                       int64_t *d_counts, int64_t *d_n_groups, int64_t *h_n_groups, float *d_mins, float *d_maxs) {
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  Workspace &w = workspace(L.device, s);
-  OpLock op_lock(w.op_mu);  // recursive: the steps below take it again; the buffers stay this call's
-  wx_launch L1 = L;
-  L1.flags &= ~(WX_F_ROW_ORDER | WX_F_SYNC);
-  const std::string rows_mode = env_or("WARPDB_GROUP_ROWS", "span");
-  // Without MIN / MAX (they come from the ordinary call): the span path
-  // straight from the table (under the same lane-order guard as below), or,
-  // when the keys are known to span more than 2048 (or the general path is
-  // asked for), the general path with its groups from the sorted keys -- no
-  // ordinary call either way
-  if (!d_mins && !d_maxs && (rows_mode == "span" || rows_mode == "general") && t->n_rows > 0) {
-    if (blank(val_expr) || blank(key_expr)) fail(WX_ERR_INVALID, "Empty query expression");
-    if (capacity < 0 || (capacity > 0 && (!d_keys || !d_sums || !d_counts)))
-      fail(WX_ERR_INVALID, "group outputs must hold `capacity` entries");
-    int route = 2;
-    if (rows_mode == "span")
-      route = rs_rank_extra(device_state(L.device, true).arch).empty()
-                  ? group_rows_direct(t, val_expr, key_expr, cond, L1, capacity, d_keys, d_sums, d_counts,
-                                      d_n_groups, h_n_groups, w, s)
-                  : 0;
-    if (route == 1) return;
-    if (route == 2) {
-      int64_t ng = -1;
-      group_rows_general(t, val_expr, key_expr, cond, L, L1, capacity, d_keys, d_sums, d_counts, d_n_groups, ng, w, s);
-      if (h_n_groups) *h_n_groups = ng;
-      return;
-    }
-  }
-  int64_t ng = 0;
-  do_group_sum(t, val_expr, key_expr, cond, &L1, key_lo, capacity, d_keys, d_sums, d_counts, d_n_groups, &ng, d_mins,
-               d_maxs);
-  if (ng > 0 && rows_mode != "general") {
-    // the groups' key span (they come out in ascending key order)
-    int32_t kk[2] = {0, 0};
-    WX_HIP(hipMemcpyAsync(&kk[0], d_keys, 4, hipMemcpyDeviceToHost, s));
-    WX_HIP(hipMemcpyAsync(&kk[1], d_keys + (ng - 1), 4, hipMemcpyDeviceToHost, s));
-    WX_HIP(hipStreamSynchronize(s));
-    const int64_t span = (int64_t)kk[1] - kk[0] + 1;
-    // the span path's stable scatter takes row order from the LDS returning
-    // same-address adds in ascending lane order -- the undocumented gfx950
-    // property the radix ranking relies on: only where rs_rank_extra allows it
-    // (elsewhere the general path's sort ranks by peer masks)
-    const bool lane_ordered_adds = rs_rank_extra(device_state(L.device, true).arch).empty();
-    if (span <= 2048 && lane_ordered_adds) {
-      group_rows_span(t, val_expr, key_expr, cond, L1, kk[0], (int)span, d_keys, d_sums, d_counts, ng, w, s,
-                      d_mins || d_maxs);
-      if (h_n_groups) *h_n_groups = ng;
-      return;
-    }
-  }
-  if (ng > 0) group_rows_general(t, val_expr, key_expr, cond, L, L1, capacity, d_keys, d_sums, d_counts, d_n_groups,
-                                 ng, w, s);
-  if (h_n_groups) *h_n_groups = ng;
-}
-
-void do_group_combine(const double *d_window, int32_t key_lo, const int32_t *xk, const double *xs, const int64_t *xc,
-                      int64_t n_extra, const wx_launch *Lp, int64_t capacity, int32_t *d_keys, double *d_sums,
-                      int64_t *d_counts, int64_t *d_n_groups, int64_t *h_n_groups) {
-  const wx_launch L = Lp ? *Lp : default_launch();
-  if (!d_window) fail(WX_ERR_INVALID, "null exchange window");
-  if (n_extra < 0 || (n_extra > 0 && (!xk || !xs || !xc))) fail(WX_ERR_INVALID, "bad out-of-window groups");
-  if (capacity < 0 || (capacity > 0 && (!d_keys || !d_sums || !d_counts)))
-    fail(WX_ERR_INVALID, "group outputs must hold `capacity` entries");
-  if ((int64_t)key_lo + WX_GROUP_WINDOW - 1 > INT32_MAX) fail(WX_ERR_INVALID, "key window out of range");
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  auto mod = util_module(L.device, true);
-  Workspace &w = workspace(L.device, s);
-  OpLock op_lock(w.op_mu);
-  int64_t *ng = d_n_groups;
-  if (!ng) {
-    ensure(w, w.g_ngroups, 8, false);
-    ng = static_cast<int64_t *>(w.g_ngroups.p);
-  }
-  WxGroupCombineArgs a;
-  a.window = d_window;
-  a.x_keys = xk;
-  a.x_sums = xs;
-  a.x_counts = reinterpret_cast<const wx_i64 *>(xc);
-  a.n_extra = n_extra;
-  a.key_lo = key_lo;
-  a.out_keys = d_keys;
-  a.out_sums = d_sums;
-  a.out_counts = reinterpret_cast<wx_i64 *>(d_counts);
-  a.capacity = capacity;
-  a.n_groups_out = reinterpret_cast<wx_i64 *>(ng);
-  launch(mod->fn("wx_group_combine"), 1, &a, s, (L.flags & WX_F_TIME) != 0, 1024);  // WX_GCOMB_BLOCK
-  if (h_n_groups) {
-    WX_HIP(hipMemcpyAsync(&w.host_word, ng, 8, hipMemcpyDeviceToHost, s));
-    WX_HIP(hipStreamSynchronize(s));
-    *h_n_groups = (int64_t)w.host_word;
-    if (*h_n_groups > capacity) fail(WX_ERR_CAPACITY, "group table / output capacity exceeded");
-  } else if (L.flags & WX_F_SYNC) {
-    WX_HIP(hipStreamSynchronize(s));
-  }
-}
-
-void check_slots(int32_t n_slots, int32_t slot_groups) {
-  if (n_slots < 1 || n_slots > WX_GROUP_EXCHANGE_MAX_SLOTS || slot_groups < 1 ||
-      (int64_t)n_slots * slot_groups > WX_GROUP_SLOT_MAX)
-    fail(WX_ERR_INVALID, "exchange slots: 1 <= n_slots <= 1024, slot_groups >= 1, n_slots * slot_groups <= 4096");
-}
-
-void do_group_combine_slots(const double *d_exchange, int32_t n_slots, int32_t slot_groups, int32_t key_lo,
-                            const wx_launch *Lp, int64_t capacity, int32_t *d_keys, double *d_sums, int64_t *d_counts,
-                            int64_t *d_n_groups, int64_t *h_n_groups) {
-  const wx_launch L = Lp ? *Lp : default_launch();
-  if (!d_exchange) fail(WX_ERR_INVALID, "null exchange buffer");
-  check_slots(n_slots, slot_groups);
-  if (capacity < 0 || (capacity > 0 && (!d_keys || !d_sums || !d_counts)))
-    fail(WX_ERR_INVALID, "group outputs must hold `capacity` entries");
-  if ((int64_t)key_lo + WX_GROUP_WINDOW - 1 > INT32_MAX) fail(WX_ERR_INVALID, "key window out of range");
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  auto mod = util_module(L.device, true);
-  Workspace &w = workspace(L.device, s);
-  OpLock op_lock(w.op_mu);
-  int64_t *ng = d_n_groups;
-  if (!ng) {
-    ensure(w, w.g_ngroups, 8, false);
-    ng = static_cast<int64_t *>(w.g_ngroups.p);
-  }
-  WxGroupSlotsArgs a;
-  a.exchange = d_exchange;
-  a.n_slots = n_slots;
-  a.slot_groups = slot_groups;
-  a.key_lo = key_lo;
-  a.out_keys = d_keys;
-  a.out_sums = d_sums;
-  a.out_counts = reinterpret_cast<wx_i64 *>(d_counts);
-  a.capacity = capacity;
-  a.n_groups_out = reinterpret_cast<wx_i64 *>(ng);
-  launch(mod->fn("wx_group_combine_slots"), 1, &a, s, (L.flags & WX_F_TIME) != 0, 1024);  // WX_GCOMB_BLOCK
-  if (h_n_groups) {
-    WX_HIP(hipMemcpyAsync(&w.host_word, ng, 8, hipMemcpyDeviceToHost, s));
-    WX_HIP(hipStreamSynchronize(s));
-    *h_n_groups = (int64_t)w.host_word;
-    if (*h_n_groups > capacity) fail(WX_ERR_CAPACITY, "group table / output capacity exceeded");
-  } else if (L.flags & WX_F_SYNC) {
-    WX_HIP(hipStreamSynchronize(s));
-  }
-}
-
-void do_group_merge_lists(const void *d_lists, int32_t n_lists, int64_t list_cap, const double *d_window,
-                          int32_t key_lo, const wx_launch *Lp, int64_t capacity, int32_t *d_keys, double *d_sums,
-                          int64_t *d_counts, int64_t *d_n_groups, int64_t *h_n_groups) {
-  const wx_launch L = Lp ? *Lp : default_launch();
-  if (n_lists < 1 || n_lists > WX_GROUP_EXCHANGE_MAX_SLOTS) fail(WX_ERR_INVALID, "1 <= n_lists <= 1024");
-  if (list_cap < 1 || list_cap > (1ll << 31)) fail(WX_ERR_INVALID, "1 <= list_capacity <= 2^31");
-  if (!d_lists) fail(WX_ERR_INVALID, "null list records");
-  if (capacity < 0 || (capacity > 0 && (!d_keys || !d_sums || !d_counts)))
-    fail(WX_ERR_INVALID, "group outputs must hold `capacity` entries");
-  if (d_window && (int64_t)key_lo + WX_GROUP_WINDOW - 1 > INT32_MAX) fail(WX_ERR_INVALID, "key window out of range");
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  auto mod = util_module(L.device, true);
-  DeviceState &d = device_state(L.device, true);
-  Workspace &w = workspace(L.device, s);
-  OpLock op_lock(w.op_mu);
-  const int64_t total = (int64_t)n_lists * list_cap;
-  const int64_t n_blk = std::max<int64_t>(1, (total + WX_GLIST_SPAN - 1) / WX_GLIST_SPAN);
-  ensure(w, w.gl_keys, (size_t)total * 4, false);
-  ensure(w, w.gl_sums, (size_t)total * 8, false);
-  ensure(w, w.gl_cnts, (size_t)total * 8, false);
-  ensure(w, w.gl_head, (size_t)total * 4, false);
-  ensure(w, w.gl_blk, (size_t)n_blk * 8, false);
-  ensure(w, w.gl_meta, 64, false);
-  int64_t *ng = d_n_groups;
-  if (!ng) {
-    ensure(w, w.g_ngroups, 8, false);
-    ng = static_cast<int64_t *>(w.g_ngroups.p);
-  }
-  WxGroupListsArgs a;
-  a.lists = static_cast<const unsigned char *>(d_lists);
-  a.list_bytes = WX_GROUP_LIST_BYTES(list_cap);
-  a.list_cap = list_cap;
-  a.sums_off = WX_GROUP_LIST_SUMS_OFF(list_cap);
-  a.counts_off = WX_GROUP_LIST_COUNTS_OFF(list_cap);
-  a.n_lists = n_lists;
-  a.key_lo = key_lo;
-  a.window = d_window;
-  a.m_keys = static_cast<int *>(w.gl_keys.p);
-  a.m_sums = static_cast<double *>(w.gl_sums.p);
-  a.m_cnts = static_cast<wx_i64 *>(w.gl_cnts.p);
-  a.m_head = static_cast<wx_u32 *>(w.gl_head.p);
-  a.blk = static_cast<wx_i64 *>(w.gl_blk.p);
-  a.n_blk = n_blk;
-  a.meta = static_cast<wx_i64 *>(w.gl_meta.p);
-  a.out_keys = d_keys;
-  a.out_sums = d_sums;
-  a.out_counts = reinterpret_cast<wx_i64 *>(d_counts);
-  a.capacity = capacity;
-  a.n_groups_out = reinterpret_cast<wx_i64 *>(ng);
-  const bool timed = (L.flags & WX_F_TIME) != 0;
-  launch(mod->fn("wx_glist_place"), grid_for(total, d.cus, 8), &a, s, timed);
-  launch(mod->fn("wx_glist_count"), (unsigned)n_blk, &a, s, timed, WX_GLIST_BLOCK);
-  launch(mod->fn("wx_glist_scan"), 1, &a, s, timed, WX_GLIST_BLOCK);
-  launch(mod->fn("wx_glist_emit"), (unsigned)n_blk, &a, s, timed, WX_GLIST_BLOCK);
-  if (h_n_groups) {
-    WX_HIP(hipMemcpyAsync(&w.host_word, ng, 8, hipMemcpyDeviceToHost, s));
-    WX_HIP(hipStreamSynchronize(s));
-    *h_n_groups = (int64_t)w.host_word;
-    if (*h_n_groups < 0) fail(WX_ERR_CAPACITY, "a shard's group list overflowed its capacity");
-    if (*h_n_groups > capacity) fail(WX_ERR_CAPACITY, "group table / output capacity exceeded");
-  } else if (L.flags & WX_F_SYNC) {
-    WX_HIP(hipStreamSynchronize(s));
-  }
-}
-
-void do_topk_merge(const wx_topk_record *recs, int32_t n_records, int32_t k, int32_t desc, const wx_launch *Lp,
-                   float *d_keys, int64_t *d_idx, float *d_vals, int64_t *d_count, int64_t *h_count) {
-  const wx_launch L = Lp ? *Lp : default_launch();
-  static_assert(sizeof(wx_topk_record) == WX_TOPK_REC_BYTES, "record layout");
-  if (k < 1 || k > WX_TOPK_MAX) fail(WX_ERR_UNSUPPORTED, "LIMIT must be between 1 and 32");
-  if (n_records < 0 || (n_records > 0 && !recs)) fail(WX_ERR_INVALID, "bad candidate records");
-  if ((int64_t)n_records * k > WX_TOPK_MERGE_MAX) fail(WX_ERR_UNSUPPORTED, "n_records * k must be <= 4096");
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  auto mod = util_module(L.device, true);
-  Workspace &w = workspace(L.device, s);
-  OpLock op_lock(w.op_mu);
-  int64_t *cnt = d_count;
-  if (!cnt && h_count) {
-    ensure(w, w.g_ngroups, 8, false);
-    cnt = static_cast<int64_t *>(w.g_ngroups.p);
-  }
-  WxTopkMergeArgs a;
-  a.records = reinterpret_cast<const unsigned char *>(recs);
-  a.n_records = n_records;
-  a.k = k;
-  a.descending = desc ? 1 : 0;
-  a.out_keys = d_keys;
-  a.out_idx = reinterpret_cast<wx_i64 *>(d_idx);
-  a.out_vals = d_vals;
-  a.count_out = reinterpret_cast<wx_i64 *>(cnt);
-  launch(mod->fn("wx_topk_merge"), 1, &a, s, (L.flags & WX_F_TIME) != 0, 1024);
-  if (h_count) {
-    WX_HIP(hipMemcpyAsync(&w.host_word, cnt, 8, hipMemcpyDeviceToHost, s));
-    WX_HIP(hipStreamSynchronize(s));
-    *h_count = (int64_t)w.host_word;
-  } else if (L.flags & WX_F_SYNC) {
-    WX_HIP(hipStreamSynchronize(s));
-  }
-}
-
-void do_cast(const void *src, int32_t sdt, void *dst, int32_t ddt, int64_t n, const wx_launch *Lp) {
-  const wx_launch L = Lp ? *Lp : default_launch();
-  if (n < 0 || (n > 0 && (!src || !dst))) fail(WX_ERR_INVALID, "bad buffer");
-  if (sdt < WX_INT32 || sdt > WX_FLOAT64 || ddt < WX_INT32 || ddt > WX_FLOAT64) fail(WX_ERR_INVALID, "bad dtype");
-  if (n == 0) return;
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  auto mod = util_module(L.device, true);
-  DeviceState &d = device_state(L.device, true);
-  WxCastArgs a;
-  a.src = src;
-  a.dst = dst;
-  a.n = n;
-  a.src_dtype = sdt;
-  a.dst_dtype = ddt;
-  launch(mod->fn("wx_cast"), grid_for(n, d.cus, 8), &a, s);
-  if (L.flags & WX_F_SYNC) WX_HIP(hipStreamSynchronize(s));
-}
-
-void do_topk(const wx_table *t, const char *order_expr, const char *cond, const char *select_expr, int32_t k,
-             int32_t desc, const wx_launch *Lp, int64_t row_base, float *d_keys, int64_t *d_idx, float *d_vals,
-             int64_t *d_count, int64_t *h_count) {
-  check_table(t);
-  const wx_launch L = Lp ? *Lp : default_launch();
-  if (blank(order_expr)) fail(WX_ERR_INVALID, "Empty ORDER BY expression");
-  if (k < 1 || k > WX_TOPK_MAX) fail(WX_ERR_UNSUPPORTED, "LIMIT must be between 1 and 32");
-  Spec spec;
-  spec.op = WX_OP_TOPK;
-  spec.cols = used_columns(t, {order_expr, cond, select_expr});
-  spec.expr = one_line(order_expr);
-  spec.cond = blank(cond) ? std::string() : one_line(cond);
-  spec.select = blank(select_expr) ? std::string() : one_line(select_expr);
-  spec.topk_k = k;
-  spec.topk_desc = desc ? 1 : 0;
-  spec.custom = read_custom(&L);
-  spec.extra = env_or("WARPDB_EXTRA_DEFINES", "");
-  spec.aligned = cols_aligned(t, spec.cols);
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  auto mod = get_module(L.device, spec, true);
-  DeviceState &d = device_state(L.device, true);
-  Workspace &w = workspace(L.device, s);
-  OpLock op_lock(w.op_mu);
-  const unsigned grid = grid_for((t->n_rows + 3) / 4, d.cus, grid_per_cu(2));  // profiles/r01/ablate_topk_grid_bound.txt: few waves publish early bounds
-  const int64_t span = (int64_t)WX_BLOCK * define_value(spec.extra, "WX_UNROLL", 8);  // quads per batch
-  const int64_t nq = (t->n_rows + 3) / 4;
-  // Seed pass (wx_topk_seed): one span per workgroup at evenly spaced
-  // offsets, ~1M rows, its exact K-th best raised into slot 0 before the
-  // scan.  WX_TOPK_SEED (diagnostic define) 0 = off, 1 = K >= 5 over tables
-  // of >= 2^24 rows (the default; WX_TOPK_SEED_MINK moves the K bound), 2 =
-  // any table of two spans or more.  Per 1e9 rows: K = 5 (C5) scan 0.607-0.612
-  // -> 0.564 ms, query 0.649-0.656 -> 0.644-0.649; K = 8 query -17..-22 us;
-  // K = 2 neutral (profiles/r06/topk_seed_k_le8.txt); K = 9 / 16 / 32 0.79 /
-  // 0.89 / 1.31 ms instead of 0.85 / 1.04 / 1.94 (profiles/r05/topk_seed.txt).
-  const int seed_mode = define_value(spec.extra, "WX_TOPK_SEED", 1);
-  const int seed_min_k = define_value(spec.extra, "WX_TOPK_SEED_MINK", 5);
-  const int64_t spans = nq / span;
-  const bool seed =
-      spans >= 2 && (seed_mode == 2 || (seed_mode == 1 && k >= seed_min_k && t->n_rows >= ((int64_t)1 << 24)));
-  const int64_t gs = seed ? std::min<int64_t>(spans, WX_TOPK_SEED_SPANS) : 0;
-  // candidates of the scan's grid, or of the seed's workgroups when a device
-  // with few CUs gives the scan the smaller grid
-  const size_t n_cand_max = (size_t)std::max<int64_t>(grid, gs) * k;
-  ensure(w, w.cand_k, n_cand_max * 4, false);
-  ensure(w, w.cand_i, n_cand_max * 8, false);
-  int64_t *cnt = d_count;
-  if (!cnt && h_count) {
-    ensure(w, w.count_tmp, 8, false);
-    cnt = static_cast<int64_t *>(w.count_tmp.p);
-  }
-  WxTopkArgs a;
-  fill_cols(t, spec.cols, a.col);
-  a.cand_k = static_cast<wx_u32 *>(w.cand_k.p);
-  a.cand_i = static_cast<wx_i64 *>(w.cand_i.p);
-  // The bound slots start at 0: zeroed when allocated, then by the previous
-  // query's finalize; a query that did not reach its finalize launch leaves
-  // them marked dirty and the next one clears them here.
-  const size_t thresh_bytes = (size_t)WX_TOPK_SLOTS * WX_TOPK_SLOT_STRIDE * 4;
-  void *old_thresh = w.topk_thresh.p;
-  ensure(w, w.topk_thresh, thresh_bytes, true);
-  if (w.topk_thresh.p != old_thresh) w.topk_clean = true;
-  if (!w.topk_clean) WX_HIP(hipMemsetAsync(w.topk_thresh.p, 0, thresh_bytes, s));
-  w.topk_clean = false;
-  a.g_thresh = static_cast<wx_u32 *>(w.topk_thresh.p);
-  a.n_rows = t->n_rows;
-  if (seed) {
-    WxTopkArgs sa = a;
-    sa.q_stride = (spans / gs) * span;
-    sa.q_step = nq;  // one batch per workgroup
-    launch(mod->fn("wx_topk_seed"), (unsigned)gs, &sa, s, false);
-    WxTopkFinArgs sf;
-    fill_cols(t, spec.cols, sf.col);
-    sf.cand_k = a.cand_k;
-    sf.cand_i = a.cand_i;
-    sf.n_cand = gs * k;
-    sf.row_base = 0;
-    sf.out_keys = nullptr;
-    sf.out_idx = nullptr;
-    sf.out_vals = nullptr;
-    sf.count_out = nullptr;
-    sf.g_thresh = a.g_thresh;
-    sf.seed = 1;
-    void *sparams[] = {&sf};
-    WX_HIP(hipModuleLaunchKernel(mod->fn("wx_topk_finalize"), 1, 1, 1, 1024, 1, 1, 0, s, sparams, nullptr));
-  }
-  a.q_stride = span;
-  a.q_step = (int64_t)grid * span;
-  launch(mod->fn("wx_topk_scan"), grid, &a, s, (L.flags & WX_F_TIME) != 0);
-  WxTopkFinArgs f;
-  fill_cols(t, spec.cols, f.col);
-  f.cand_k = a.cand_k;
-  f.cand_i = a.cand_i;
-  f.n_cand = (wx_i64)grid * k;
-  f.row_base = row_base;
-  f.out_keys = d_keys;
-  f.out_idx = reinterpret_cast<wx_i64 *>(d_idx);
-  f.out_vals = d_vals;
-  f.count_out = reinterpret_cast<wx_i64 *>(cnt);
-  f.g_thresh = a.g_thresh;
-  f.seed = 0;
-  void *params[] = {&f};
-  WX_HIP(hipModuleLaunchKernel(mod->fn("wx_topk_finalize"), 1, 1, 1, 1024, 1, 1, 0, s, params, nullptr));  // WX_FIN_BLOCK
-  w.topk_clean = true;
-  if ((L.flags & WX_F_SYNC) || h_count) check_errors(w);
-  if (h_count) WX_HIP(hipMemcpy(h_count, cnt, 8, hipMemcpyDeviceToHost));
-}
-
-std::shared_ptr<Module> util_module(int dev, bool load, const std::string &more) {
-  Spec spec;
-  spec.op = WX_OP_UTIL;
-  spec.extra = env_or("WARPDB_EXTRA_DEFINES", "") + more;  // diagnostics / tuning only
-  return get_module(dev, spec, load);
-}
-
-// Radix tile geometry (workgroup size x keys per lane), measured per kind
-// in one process per A/B (profiles/r05/ab_sort_geometry.txt): keys alone
-// 1024 x 32 (one 147 KB workgroup per CU; 10.75-11.3 ms per 1e9 keys against
-// 11.45 for round 4's 512 x 32, whose two workgroups per CU walk twice the
-// look-back chains; with the permutation ahead of the look-back and plain
-// stores 8.67 ms, ab_sort_split_store.txt) with three predecessor words per
-// look-back round -- the util module's default; key + payload 512 x 28 (one
-// 120 KB workgroup per CU, 18.5 ms per 1e9 pairs against 20.8 for 512 x 20;
-// 512 x 32 spills, 23.5) with four, a module of its own.  A diagnostic build
-// may set WX_RS_BLOCK / WX_RS_ITEMS in $WARPDB_EXTRA_DEFINES; the host reads
-// them back from there so its tile count matches the kernel's.  rs_geometry
-// returns the extra defines of the module with the kernels.
-// The in-wave ranking by one returning LDS add per key (WX_RS_RANK_ATOMIC)
-// is stable only because the LDS returns same-address results in ascending
-// lane order -- observed and tested on gfx950, not documented.  Any other
-// target builds the peer-mask ranking (WX_RS_RANK_ATOMIC=0) until its own
-// heavy-tie sort tests pass with the atomic form ($WARPDB_RS_RANK_ATOMIC=1
-// forces it, =0 forbids it: a test hook for both forms).
-std::string rs_rank_extra(const std::string &arch) {
-  const std::string f = env_or("WARPDB_RS_RANK_ATOMIC", "");
-  if (f == "1") return "";
-  if (f == "0" || arch.compare(0, 6, "gfx950") != 0) return ",WX_RS_RANK_ATOMIC=0";
-  return "";
-}
-
-std::string rs_geometry(bool pairs, int *items, int *block, const std::string &arch) {
-  const std::string extra = env_or("WARPDB_EXTRA_DEFINES", "");
-  *items = define_value(extra, "WX_RS_ITEMS", pairs ? 28 : WX_RS_ITEMS);
-  *block = define_value(extra, "WX_RS_BLOCK", pairs ? 512 : WX_RS_BLOCK);
-  if (*block < 256 || *block > 1024 || *block % 64) fail(WX_ERR_INVALID, "WX_RS_BLOCK must be 256..1024, a multiple of 64");
-  if (*items < 1 || *items > 64) fail(WX_ERR_INVALID, "WX_RS_ITEMS must be 1..64");
-  const std::string rank = rs_rank_extra(arch);
-  if (!pairs) return rank;
-  return ",WX_RS_ITEMS=" + std::to_string(*items) + ",WX_RS_BLOCK=" + std::to_string(*block) +
-         ",WX_RS_LBW=4" + rank;
-}
-
-// Stable LSD radix sort (wx_radix_hist + up to four wx_radix_tile_*):
-// `d_a` holds float values (kind 0) or int keys (kind 1, `d_v` their float
-// payload); the sorted result ends in the caller's buffers.
-// `src0` (keys only, nullable): the first pass reads the keys from there
-// instead of `d_a` (ORDER BY a bare column: the column itself, no projection
-// copy); `src0` is never written and the result still ends in `d_a`.
-void radix_sort(void *d_a, float *d_v, int64_t count, int kind, int32_t ascending, const wx_launch &L, Workspace &w,
-                hipStream_t s, int64_t limit, const void *src0, void **res_k, float **res_v, const float *src_v) {
-  if (src0 == d_a) src0 = nullptr;
-  const void *in_k = src0 ? src0 : d_a;
-  int items = 0, rs_block = 0;
-  const std::string more = rs_geometry(d_v != nullptr, &items, &rs_block, device_state(L.device, true).arch);
-  const int64_t rs_tile = (int64_t)items * rs_block;
-  auto mod = util_module(L.device, true, more);
-  DeviceState &d = device_state(L.device, true);
-  const bool timed = (L.flags & WX_F_TIME) != 0;
-  // [0, 1024): the four digit histograms; [1024, 2048): digit bases;
-  // [2048]: a float key was NaN or -0.0 (the general order map is needed)
-  ensure(w, w.rs_hist, 2 * 1024 * 4 + 256, false);
-  wx_u32 *hist = static_cast<wx_u32 *>(w.rs_hist.p), *bases = hist + 1024;
-  WX_HIP(hipMemsetAsync(hist, 0, 1024 * 4, s));
-  WX_HIP(hipMemsetAsync(hist + 2048, 0, 4, s));
-  WxRadixHistArgs h;
-  h.src = static_cast<const wx_u32 *>(in_k);
-  h.n = count;
-  h.hist = hist;
-  h.aligned = aligned16(in_k) ? 1 : 0;
-  const std::string hname = std::string("wx_radix_hist_") + (kind == 0 ? "f_" : "i_") + (ascending ? "a" : "d");
-  // one 1024-thread workgroup per CU (128 KB of counters)
-  launch(mod->fn(hname.c_str()), grid_for((count + 15) / 16 / 4, d.cus, 1), &h, s, timed, 1024);
-  std::vector<wx_u32> hh(1025), base(1024);
-  WX_HIP(hipMemcpyAsync(hh.data(), hist, 1024 * 4, hipMemcpyDeviceToHost, s));
-  WX_HIP(hipMemcpyAsync(hh.data() + 1024, hist + 2048, 4, hipMemcpyDeviceToHost, s));
-  WX_HIP(hipStreamSynchronize(s));
-  // float keys with no NaN and no -0.0: the tile kernels' plain order flip
-  // (same order, 2 ops instead of 9 per digit; $WARPDB_RS_PLAIN=0 turns it off)
-  const bool plain = kind == 0 && hh[1024] == 0 && env_or("WARPDB_RS_PLAIN", "1") != "0";
-  bool skip[4];
-  for (int p = 0; p < 4; ++p) {
-    uint64_t run = 0;
-    skip[p] = false;
-    for (int dg = 0; dg < 256; ++dg) {
-      base[p * 256 + dg] = (wx_u32)run;
-      run += hh[p * 256 + dg];
-      if ((int64_t)hh[p * 256 + dg] == count) skip[p] = true;  // one digit for every key: identity pass
-    }
-    if ((int64_t)run != count)
-      fail(WX_ERR_INTERNAL, "radix histogram does not add up (digit " + std::to_string(p) + ": " +
-                                std::to_string(run) + " of " + std::to_string(count) + " keys)");
-  }
-  WX_HIP(hipMemcpyAsync(bases, base.data(), 1024 * 4, hipMemcpyHostToDevice, s));
-  const int64_t n_tiles = (count + rs_tile - 1) / rs_tile;
-  const size_t status_bytes = (size_t)n_tiles * 256 * 8;
-  void *old_status = w.rs_status.p;
-  ensure(w, w.rs_status, status_bytes, true);
-  if (w.rs_status.p != old_status) w.rs_epoch = 0;  // fresh, zeroed words
-  // [2 * pass]: ticket, abort; words 16..47: diagnostic look-back statistics;
-  // words 64..191: diagnostic phase times (u64, 8 per pass)
-  ensure(w, w.rs_ctl, 1024, false);
-  WX_HIP(hipMemsetAsync(w.rs_ctl.p, 0, 1024, s));
-  ensure(w, w.rs_tmp_k, (size_t)count * 4, false);
-  if (d_v) ensure(w, w.rs_tmp_v, (size_t)count * 4, false);
-  void *cur_k = const_cast<void *>(in_k), *alt_k = w.rs_tmp_k.p;
-  // src_v (with d_v): the first executed pass reads the payload from there
-  // instead of d_v, and the passes then ping-pong between the scratch and d_v
-  // (src_v is never written)
-  void *cur_v = d_v && src_v ? const_cast<float *>(src_v) : d_v, *alt_v = d_v ? w.rs_tmp_v.p : nullptr;
-  // One kernel per (payload, key kind, direction): the key map is compiled
-  // in.  One workgroup per tile, tiles in ticket order.
-  const std::string kname = std::string("wx_radix_tile_") + (d_v ? "kv_" : "k_") +
-                            (kind == 0 ? (plain ? "fp_" : "f_") : "i_") + (ascending ? "a" : "d");
-  hipFunction_t fn = mod->fn(kname.c_str());
-  const unsigned grid = (unsigned)n_tiles;  // one tile per workgroup (persistent workgroups measured 3.3x slower)
-  // ORDER BY .. LIMIT: only the first `limit` keys of the sorted order are
-  // wanted.  They all lie in the top-digit buckets up to the one holding
-  // rank limit - 1 (cumulative count `head`); one stable pass on the top
-  // digit moves those buckets, in order, to the front, and only that head
-  // is sorted in full.  Worth it when the head is a small part of the array.
-  int64_t head = count;
-  if (limit >= 0 && limit < count && !skip[3]) {
-    int64_t run = 0;
-    for (int dg = 0; dg < 256 && run < std::max<int64_t>(limit, 1); ++dg) run += hh[3 * 256 + dg];
-    if (run <= count / 4) head = run;
-  }
-  const bool partial = head < count;
-  if (src0) {  // ping-pong between d_a and the scratch so that the last executed pass writes d_a
-    int executed = 0;
-    for (int p = partial ? 3 : 0; p < 4; ++p) executed += skip[p] ? 0 : 1;
-    alt_k = executed % 2 ? d_a : w.rs_tmp_k.p;
-  }
-  for (int p = partial ? 3 : 0; p < 4; ++p) {
-    if (skip[p]) continue;
-    if (++w.rs_epoch > WX_RS_EPOCHS) {  // epoch numbers exhausted: clear every word once
-      WX_HIP(hipMemsetAsync(w.rs_status.p, 0, w.rs_status.bytes, s));
-      w.rs_epoch = 1;
-    }
-    WxRadixPassArgs a;
-    a.src_k = static_cast<const wx_u32 *>(cur_k);
-    a.dst_k = static_cast<wx_u32 *>(alt_k);
-    a.src_v = static_cast<const wx_u32 *>(cur_v);
-    a.dst_v = static_cast<wx_u32 *>(alt_v);
-    a.digit_base = bases + p * 256;
-    a.status = static_cast<wx_u64 *>(w.rs_status.p);
-    a.ctl = static_cast<wx_u32 *>(w.rs_ctl.p) + 2 * p;
-    a.err = reinterpret_cast<wx_u32 *>(static_cast<wx_u64 *>(w.ctrs.p) + 1);
-    a.lbd = static_cast<wx_u64 *>(w.ctrs.p) + WX_LBD_BASE;
-    a.n = count;
-    a.shift = 8 * p;
-    a.kind = kind;
-    a.ascending = ascending ? 1 : 0;
-    a.epoch = w.rs_epoch;
-    // lane 0's digit group ranked by one ballot (a few-valued digit -- the
-    // exponent byte of uniform floats, ~60 % on one value -- would serialize
-    // the ranking's LDS adds on one counter).  On every pass: ranking by the
-    // plain LDS add on the passes without a skewed digit ($WARPDB_RS_LEAD=auto:
-    // where no digit holds > 1/16 of the keys) measured slower, keys 12.37 vs
-    // 12.24 ms per 1e9, pairs 18.02 vs 18.05 (profiles/r03/abl_sort_plain_lead.txt)
-    uint32_t top = 0;
-    for (int dg = 0; dg < 256; ++dg) top = std::max<uint32_t>(top, hh[p * 256 + dg]);
-    const std::string lead_env = env_or("WARPDB_RS_LEAD", "1");
-    a.lead = lead_env == "1" ? 1 : lead_env == "0" ? 0 : ((int64_t)top * 16 > count ? 1 : 0);
-    launch(fn, grid, &a, s, timed, (unsigned)rs_block);
-    cur_k = alt_k;
-    alt_k = cur_k == d_a ? w.rs_tmp_k.p : d_a;  // never src0
-    const bool from_src_v = d_v && src_v && cur_v == src_v;
-    std::swap(cur_v, alt_v);
-    if (from_src_v) alt_v = d_v;  // never src_v
-  }
-  if (partial) {  // the head, still in input order within each bucket, then a full sort of it
-    if (cur_k != d_a) WX_HIP(hipMemcpyAsync(d_a, cur_k, (size_t)head * 4, hipMemcpyDeviceToDevice, s));
-    if (d_v) WX_HIP(hipMemcpyAsync(d_v, cur_v, (size_t)head * 4, hipMemcpyDeviceToDevice, s));
-    WX_HIP(hipStreamSynchronize(s));  // `base` (pageable) must outlive its copy
-    radix_sort(d_a, d_v, head, kind, ascending, L, w, s);
-    return;
-  }
-  if (res_k) {  // the caller reads the sorted keys (and payload) wherever the last pass left them
-    *res_k = cur_k;
-    if (res_v) *res_v = static_cast<float *>(cur_v);
-  } else {
-    if (cur_k != d_a) WX_HIP(hipMemcpyAsync(d_a, cur_k, (size_t)count * 4, hipMemcpyDeviceToDevice, s));
-    // (the payload's ping-pong need not end where the keys' does once either starts from a source)
-    if (d_v && cur_v != d_v) WX_HIP(hipMemcpyAsync(d_v, cur_v, (size_t)count * 4, hipMemcpyDeviceToDevice, s));
-  }
-  WX_HIP(hipStreamSynchronize(s));  // `base` (pageable) must outlive its copy; the legacy sorts are synchronous
-}
-
-// Stable sort of `count` 4-byte payloads by a 32-bit rank: LSD radix sort,
-// or the bitonic network with WARPDB_SORT=bitonic (comparison runs only).
-void do_sort(void *d_a, float *d_v, int64_t count, int kind, int32_t ascending, const wx_launch *Lp,
-             int64_t limit = -1, const void *src = nullptr) {
-  const wx_launch L = Lp ? *Lp : default_launch();
-  if (count < 0 || count > 0xffffffffll) fail(WX_ERR_INVALID, "bad element count");
-  if (src == d_a) src = nullptr;
-  if (!src && (count <= 1 || limit == 0)) return;
-  if (count == 0) return;
-  if (!d_a) fail(WX_ERR_INVALID, "null buffer");
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  if (src && (count <= 1 || limit == 0 || env_or("WARPDB_SORT", "radix") == "bitonic")) {
-    // nothing to sort, or the bitonic network (in place): the keys first
-    WX_HIP(hipMemcpyAsync(d_a, src, (size_t)count * 4, hipMemcpyDeviceToDevice, s));
-    WX_HIP(hipStreamSynchronize(s));  // synchronous like every sort entry point
-    src = nullptr;
-  }
-  if (count <= 1 || limit == 0) return;
-  Workspace &w = workspace(L.device, s);
-  OpLock op_lock(w.op_mu);
-  if (env_or("WARPDB_SORT", "radix") != "bitonic") {
-    radix_sort(d_a, d_v, count, kind, ascending, L, w, s, limit, src);
-    if (L.flags & WX_F_SYNC) check_errors(w);
-    return;
-  }
-  auto mod = util_module(L.device, true);
-  DeviceState &d = device_state(L.device, true);
-  int64_t npad = WX_SORT_LDS;
-  while (npad < count) npad <<= 1;
-  ensure(w, w.sort_keys, (size_t)npad * 8, false);
-  ensure(w, w.sort_copy_a, (size_t)count * 4, false);
-  WX_HIP(hipMemcpyAsync(w.sort_copy_a.p, d_a, (size_t)count * 4, hipMemcpyDeviceToDevice, s));
-  if (d_v) {
-    ensure(w, w.sort_copy_v, (size_t)count * 4, false);
-    WX_HIP(hipMemcpyAsync(w.sort_copy_v.p, d_v, (size_t)count * 4, hipMemcpyDeviceToDevice, s));
-  }
-  WxSortPrepArgs p;
-  p.src = w.sort_copy_a.p;
-  p.keys = static_cast<wx_u64 *>(w.sort_keys.p);
-  p.n = count;
-  p.npad = npad;
-  p.kind = kind;
-  p.ascending = ascending ? 1 : 0;
-  launch(mod->fn("wx_sort_prep"), grid_for(npad, d.cus, 8), &p, s);
-  bitonic_u64(L.device, p.keys, npad, s);
-  WxSortApplyArgs ap;
-  ap.keys = p.keys;
-  ap.n = count;
-  ap.src_a = w.sort_copy_a.p;
-  ap.dst_a = d_a;
-  ap.src_v = d_v ? static_cast<const float *>(w.sort_copy_v.p) : nullptr;
-  ap.dst_v = d_v;
-  launch(mod->fn("wx_sort_apply"), grid_for(count, d.cus, 8), &ap, s);
-  if (L.flags & WX_F_SYNC) check_errors(w);
-}
-
-// ORDER BY .. LIMIT head of one shard (any limit): ordered compaction of the
-// key (and of the SELECT expression when it differs) with shard-local rows,
-// a stable key sort of the positions limited to the head, the head gathered
-// into the record.
-void do_order_head(const wx_table *t, const char *order_expr, const char *cond, const char *select_expr, int64_t limit,
-                   int32_t desc, const wx_launch *Lp, int64_t row_base, void *d_record, int64_t cap) {
-  check_table(t);
-  const wx_launch L0 = Lp ? *Lp : default_launch();
-  if (blank(order_expr)) fail(WX_ERR_INVALID, "Empty ORDER BY expression");
-  if (limit < 0 || cap < limit || !d_record) fail(WX_ERR_INVALID, "head record must hold `limit` rows");
-  // the passing rows' local ids are compacted as int32 (WxHeadArgs.rows)
-  if (t->n_rows > INT32_MAX) fail(WX_ERR_UNSUPPORTED, "ORDER BY .. LIMIT head: a shard holds at most 2^31 - 1 rows");
-  wx_launch L = L0;
-  L.flags &= ~(int32_t)WX_F_TIME;
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  auto mod = util_module(L.device, true);
-  DeviceState &d = device_state(L.device, true);
-  Workspace &w = workspace(L.device, s);
-  OpLock op_lock(w.op_mu);
-  const size_t n = (size_t)std::max<int64_t>(1, t->n_rows);
-  ensure(w, w.hd_keys, n * 4, false);
-  ensure(w, w.hd_rows, n * 4, false);
-  ensure(w, w.hd_idx, n * 4, false);
-  ensure(w, w.hd_count, 8, false);
-  const bool same = blank(select_expr) || one_line(select_expr) == one_line(order_expr);
-  int64_t count = 0;
-  do_project_filter(t, order_expr, cond, &L, WX_MODE_COMPACT, static_cast<float *>(w.hd_keys.p), w.hd_rows.p, 4, 0,
-                    static_cast<int64_t *>(w.hd_count.p), &count);
-  if (!same) {
-    ensure(w, w.hd_vals, n * 4, false);
-    int64_t c2 = 0;
-    do_project_filter(t, select_expr, cond, &L, WX_MODE_COMPACT, static_cast<float *>(w.hd_vals.p), nullptr, 0, 0,
-                      nullptr, &c2);
-    if (c2 != count) fail(WX_ERR_INTERNAL, "ORDER BY rows differ from SELECT rows");
-  }
-  WxHeadArgs a{};
-  a.n = count;
-  a.idx = static_cast<wx_u32 *>(w.hd_idx.p);
-  if (count > 0) launch(mod->fn("wx_iota"), grid_for(count, d.cus, 8), &a, s);
-  const int64_t m = std::min(count, limit);
-  if (m > 0) do_sort(w.hd_keys.p, static_cast<float *>(w.hd_idx.p), count, 0, desc ? 0 : 1, &L, m);
-  a.keys = static_cast<const float *>(w.hd_keys.p);
-  a.vals = same ? nullptr : static_cast<const float *>(w.hd_vals.p);
-  a.rows = static_cast<const int *>(w.hd_rows.p);
-  a.row_base = row_base;
-  a.count = static_cast<const wx_i64 *>(w.hd_count.p);
-  a.limit = limit;
-  a.record = static_cast<unsigned char *>(d_record);
-  a.cap = cap;
-  launch(mod->fn("wx_head_gather"), grid_for(std::max<int64_t>(1, m), d.cus, 8), &a, s);
-  WX_HIP(hipStreamSynchronize(s));  // synchronous (the workspace's scratch is reused by the next call)
-  if (L.flags & WX_F_SYNC) check_errors(w);
-}
-
-// ------------------------------------------------------------- row gather
-// Gather geometry (wx_gather.hip): threads per workgroup and quads per
-// thread whose loads are issued together, per output count
-// (profiles/select_ordered_geometry.txt); WX_GATHER_BLOCK / _UNROLL of the
-// define list override it.
-void gather_geometry(Spec &spec, int nout) {
-  static const int kUnroll[WX_GATHER_MAX_OUT + 1] = {0, WX_GATHER_UNROLL, WX_GATHER_UNROLL, WX_GATHER_UNROLL,
-                                                     WX_GATHER_UNROLL};
-  const std::string extra = env_or("WARPDB_EXTRA_DEFINES", "");
-  spec.gblock = define_value(extra, "WX_GATHER_BLOCK", WX_GATHER_BLOCK);
-  spec.gunroll = define_value(extra, "WX_GATHER_UNROLL", kUnroll[nout]);
-  if (spec.gblock < 64 || spec.gblock > 1024 || (spec.gblock & 63) || spec.gunroll < 1 || spec.gunroll > 8)
-    fail(WX_ERR_INVALID, "row gather geometry out of range (64..1024 threads in whole waves, 1..8 quads per thread)");
-}
-
-Spec gather_spec(const wx_table *t, const char *const *exprs, int32_t n_exprs, const wx_launch &L) {
-  Spec spec;
-  spec.op = WX_OP_GATHER;
-  gather_geometry(spec, n_exprs);
-  spec.cols = used_columns(t, std::vector<const char *>(exprs, exprs + n_exprs));
-  spec.expr = one_line(exprs[0]);
-  for (int32_t j = 1; j < n_exprs; ++j) spec.more.push_back(one_line(exprs[j]));
-  spec.custom = read_custom(&L);
-  spec.extra = env_or("WARPDB_EXTRA_DEFINES", "");
-  return spec;
-}
-
-// The argument checks of a gather that need no device.
-void check_gather_args(const wx_table *t, const char *const *exprs, int32_t n_exprs, int32_t idx_bytes, int64_t count) {
-  check_table(t);
-  check_select_exprs(exprs, n_exprs);
-  if (idx_bytes != 4 && idx_bytes != 8) fail(WX_ERR_INVALID, "idx_bytes must be 4 or 8");
-  if (count < 0) fail(WX_ERR_INVALID, "negative row id count");
-}
-
-// n_exprs expressions at `count` row ids (wx_gather.hip), bounded on the
-// device by *d_count when given.
-void do_gather_multi(const wx_table *t, const char *const *exprs, int32_t n_exprs, const void *d_rows,
-                     int32_t idx_bytes, int64_t row_base, int64_t count, const int64_t *d_count, const wx_launch *Lp,
-                     float *const *d_out_vals, int64_t *d_out_rows, int64_t out_row_base) {
-  check_gather_args(t, exprs, n_exprs, idx_bytes, count);
-  if (count > 0 && !d_rows) fail(WX_ERR_INVALID, "null row id buffer");
-  const wx_launch L = Lp ? *Lp : default_launch();
-  if (count == 0) return;
-  const Spec spec = gather_spec(t, exprs, n_exprs, L);
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  auto mod = get_module(L.device, spec, true);
-  DeviceState &d = device_state(L.device, true);
-  Workspace &w = workspace(L.device, s);
-  OpLock op_lock(w.op_mu);
-  WxGatherArgs a;
-  fill_cols(t, spec.cols, a.col);
-  a.rows = d_rows;
-  a.d_count = reinterpret_cast<const wx_i64 *>(d_count);
-  for (int j = 0; j < WX_GATHER_MAX_OUT; ++j) a.out_val[j] = j < n_exprs && d_out_vals ? d_out_vals[j] : nullptr;
-  a.out_rows = reinterpret_cast<wx_i64 *>(d_out_rows);
-  a.count = count;
-  a.n_rows = t->n_rows;
-  a.row_base = row_base;
-  a.out_row_base = out_row_base;
-  a.idx64 = idx_bytes == 8;
-  // every CU full of waves (2048 threads): a random gather lives on the
-  // number of independent misses in flight
-  const int64_t tile = (int64_t)spec.gblock * 4 * spec.gunroll;
-  const int64_t tiles = (count + tile - 1) / tile;
-  const unsigned grid = (unsigned)std::min<int64_t>(tiles, (int64_t)d.cus * std::max(1, 2048 / spec.gblock));
-  launch(mod->fn("wx_select_gather"), grid, &a, s, (L.flags & WX_F_TIME) != 0, (unsigned)spec.gblock);
-  if (L.flags & WX_F_SYNC) check_errors(w);
-}
-
-// ORDER BY order_expr [DESC] [LIMIT] over a multi-column SELECT: the sorted
-// row ids once (top-K scan, or key compaction + stable pair sort with the
-// row ids as the payload), then the expressions gathered at those rows in
-// chunks of WX_MAX_OUTPUTS.
-void do_select_ordered(const wx_table *t, const char *const *exprs, int32_t n_exprs, const char *cond,
-                       const char *order_expr, int32_t desc, int64_t limit, const wx_launch *Lp, int64_t row_base,
-                       float *const *d_out_vals, float *d_out_keys, int64_t *d_out_rows, int64_t capacity,
-                       int64_t *d_count, int64_t *h_count) {
-  check_table(t);
-  if (n_exprs < 0 || n_exprs > WX_ORDERED_MAX_EXPRS || (n_exprs > 0 && !exprs))
-    fail(WX_ERR_INVALID, "n_exprs must be between 0 and " + std::to_string(WX_ORDERED_MAX_EXPRS));
-  for (int32_t j = 0; j < n_exprs; ++j)
-    if (blank(exprs[j])) fail(WX_ERR_INVALID, "Empty query expression");
-  if (blank(order_expr)) fail(WX_ERR_INVALID, "Empty ORDER BY expression");
-  if (capacity < 0) fail(WX_ERR_INVALID, "negative output capacity");
-  if (limit < 0) limit = INT64_MAX;
-  const wx_launch L0 = Lp ? *Lp : default_launch();
-  DevGuard g(L0.device);
-  hipStream_t s = static_cast<hipStream_t>(L0.stream);
-  if (limit == 0 || t->n_rows == 0) {  // nothing to order: no launch
-    if (d_count) WX_HIP(hipMemsetAsync(d_count, 0, 8, s));
-    if (h_count) *h_count = 0;
-    return;
-  }
-  Workspace &w = workspace(L0.device, s);
-  OpLock op_lock(w.op_mu);
-  wx_launch L = L0;  // the inner calls: no per-call sync, no timing of a part
-  L.flags &= ~(uint32_t)(WX_F_TIME | WX_F_SYNC);
-  // the expressions at the rows, four at a time (chunks with no output wanted are skipped)
-  auto gather = [&](const void *rows, int32_t idx_bytes, int64_t rows_base, int64_t count, const int64_t *dc,
-                    int64_t *out_rows) {
-    bool rows_done = out_rows == nullptr;
-    for (int32_t c = 0; c < n_exprs; c += WX_MAX_OUTPUTS) {
-      const int32_t m = std::min<int32_t>(WX_MAX_OUTPUTS, n_exprs - c);
-      bool any = false;
-      for (int32_t j = 0; j < m; ++j) any = any || (d_out_vals && d_out_vals[c + j]);
-      if (!any) continue;
-      do_gather_multi(t, exprs + c, m, rows, idx_bytes, rows_base, count, dc, &L, d_out_vals + c,
-                      rows_done ? nullptr : out_rows, row_base);
-      rows_done = true;
-    }
-    if (!rows_done) {  // rows only: a constant expression reads no column
-      const char *none[1] = {"0.0f"};
-      do_gather_multi(t, none, 1, rows, idx_bytes, rows_base, count, dc, &L, nullptr, out_rows, row_base);
-    }
-  };
-  const bool topk_route = limit <= WX_TOPK_MAX && env_or("WARPDB_ORDERED_ROUTE", "auto") != "sort";
-  if (topk_route) {
-    // keys, global rows and the device count from one scan; a caller whose
-    // buffers could be too short gets them through the workspace, after a
-    // host read of the count
-    const bool direct = capacity >= limit;
-    ensure(w, w.so_keys, WX_TOPK_MAX * 4, false);
-    ensure(w, w.so_rows, WX_TOPK_MAX * 8, false);
-    ensure(w, w.so_cnt, 8, false);
-    float *keys = direct ? d_out_keys : static_cast<float *>(w.so_keys.p);
-    int64_t *rows = direct && d_out_rows ? d_out_rows : static_cast<int64_t *>(w.so_rows.p);
-    int64_t *cnt = d_count ? d_count : static_cast<int64_t *>(w.so_cnt.p);
-    int64_t count = 0;
-    do_topk(t, order_expr, cond, nullptr, (int32_t)limit, desc, &L, row_base, keys, rows, nullptr, cnt,
-            direct ? nullptr : &count);
-    if (!direct) {
-      if (count > capacity) {
-        if (h_count) *h_count = count;
-        fail(WX_ERR_CAPACITY, "ordered SELECT: the result holds " + std::to_string(count) + " rows, capacity is " +
-                                  std::to_string(capacity));
-      }
-      if (d_out_keys && count) WX_HIP(hipMemcpyAsync(d_out_keys, keys, (size_t)count * 4, hipMemcpyDeviceToDevice, s));
-      if (d_out_rows && count) WX_HIP(hipMemcpyAsync(d_out_rows, rows, (size_t)count * 8, hipMemcpyDeviceToDevice, s));
-    }
-    gather(rows, 8, row_base, direct ? limit : count, cnt, nullptr);
-    if ((L0.flags & WX_F_SYNC) || h_count) check_errors(w);
-    if (h_count) WX_HIP(hipMemcpy(h_count, cnt, 8, hipMemcpyDeviceToHost));
-    return;
-  }
-  // the passing rows' local ids are compacted as int32 and sorted as the key's 4-byte payload
-  if (t->n_rows > INT32_MAX) fail(WX_ERR_UNSUPPORTED, "ordered SELECT: a table holds at most 2^31 - 1 rows");
-  const size_t n = (size_t)std::max<int64_t>(1, t->n_rows);
-  ensure(w, w.hd_keys, n * 4, false);
-  ensure(w, w.hd_rows, n * 4, false);
-  ensure(w, w.hd_count, 8, false);
-  int64_t count = 0;
-  do_project_filter(t, order_expr, cond, &L, WX_MODE_COMPACT, static_cast<float *>(w.hd_keys.p), w.hd_rows.p, 4, 0,
-                    static_cast<int64_t *>(w.hd_count.p), &count);
-  const int64_t m = std::min(count, limit);
-  if (m > capacity) {
-    if (h_count) *h_count = m;
-    fail(WX_ERR_CAPACITY, "ordered SELECT: the result holds " + std::to_string(m) + " rows, capacity is " +
-                              std::to_string(capacity));
-  }
-  if (m > 0) {
-    do_sort(w.hd_keys.p, static_cast<float *>(w.hd_rows.p), count, 0, desc ? 0 : 1, &L, m);
-    if (d_out_keys) WX_HIP(hipMemcpyAsync(d_out_keys, w.hd_keys.p, (size_t)m * 4, hipMemcpyDeviceToDevice, s));
-    gather(w.hd_rows.p, 4, 0, m, nullptr, d_out_rows);
-  }
-  if (d_count) WX_HIP(hipMemcpyAsync(d_count, &m, 8, hipMemcpyHostToDevice, s));
-  WX_HIP(hipStreamSynchronize(s));  // synchronous (the workspace's scratch is reused by the next call; &m)
-  if (L0.flags & WX_F_SYNC) check_errors(w);
-  if (h_count) *h_count = m;
-}
-
-void do_head_merge(const void *recs, int32_t n_records, int64_t cap, int64_t limit, int32_t desc, const wx_launch *Lp,
-                   float *d_keys, int64_t *d_rows, float *d_vals, int64_t *d_count, int64_t *h_count) {
-  const wx_launch L0 = Lp ? *Lp : default_launch();
-  if (n_records < 0 || n_records > 1024 || (n_records > 0 && !recs)) fail(WX_ERR_INVALID, "bad head records");
-  if (cap < 0 || limit < 0 || (int64_t)n_records * cap >= (1ll << 32)) fail(WX_ERR_INVALID, "bad head capacity");
-  wx_launch L = L0;
-  L.flags &= ~(int32_t)WX_F_TIME;
-  DevGuard g(L.device);
-  hipStream_t s = static_cast<hipStream_t>(L.stream);
-  auto mod = util_module(L.device, true);
-  DeviceState &d = device_state(L.device, true);
-  Workspace &w = workspace(L.device, s);
-  OpLock op_lock(w.op_mu);
-  const size_t nc = (size_t)std::max<int64_t>(1, (int64_t)n_records * cap);
-  ensure(w, w.hm_keys, nc * 4, false);
-  ensure(w, w.hm_idx, nc * 4, false);
-  ensure(w, w.hm_count, 8, false);
-  WxHeadArgs a{};
-  a.records = static_cast<const unsigned char *>(recs);
-  a.n_records = n_records;
-  a.cap = cap;
-  a.cat_keys = static_cast<float *>(w.hm_keys.p);
-  a.cat_idx = static_cast<wx_u32 *>(w.hm_idx.p);
-  a.cat_count = static_cast<wx_i64 *>(w.hm_count.p);
-  launch(mod->fn("wx_head_concat"), 1, &a, s, false, 1024);
-  int64_t total = 0;
-  WX_HIP(hipMemcpyAsync(&w.host_word, a.cat_count, 8, hipMemcpyDeviceToHost, s));
-  WX_HIP(hipStreamSynchronize(s));
-  total = (int64_t)w.host_word;
-  const int64_t m = std::min(total, limit);
-  if (m > 0) do_sort(w.hm_keys.p, static_cast<float *>(w.hm_idx.p), total, 0, desc ? 0 : 1, &L, m);
-  int64_t *cnt = d_count;
-  if (!cnt) {
-    ensure(w, w.count_tmp, 8, false);
-    cnt = static_cast<int64_t *>(w.count_tmp.p);
-  }
-  a.idx = a.cat_idx;
-  a.keys = a.cat_keys;
-  a.count = a.cat_count;
-  a.limit = limit;
-  a.out_keys = d_keys;
-  a.out_rows = reinterpret_cast<wx_i64 *>(d_rows);
-  a.out_vals = d_vals;
-  a.count_out = reinterpret_cast<wx_i64 *>(cnt);
-  launch(mod->fn("wx_head_emit"), grid_for(std::max<int64_t>(1, m), d.cus, 8), &a, s);
-  if (h_count) *h_count = m;
-  WX_HIP(hipStreamSynchronize(s));
-  if (L.flags & WX_F_SYNC) check_errors(w);
-}
-
-}  // namespace
+//
+// This file is the C ABI alone: argument checks that belong to an entry point
+// and the call into the family's host code (DESIGN.md 2 has the file table).
+#include "wx_host.hpp"
+
+using namespace wx;
 
 // ======================================================================= ABI
 extern "C" {
@@ -2897,16 +41,8 @@ wx_status wx_prepare_multi(const wx_table *table, const char *const *exprs, int3
   return guarded(err, errlen, [&] {
     check_table(table);
     check_select_exprs(exprs, n_exprs);
-    const wx_launch L = launch_ ? *launch_ : default_launch();
-    const Spec spec = select_spec(table, exprs, n_exprs, cond, L);
-    int ndev = 0;
-    const bool have_gpu = hipGetDeviceCount(&ndev) == hipSuccess && ndev > L.device;
-    if (have_gpu) {
-      DevGuard g(L.device);
-      get_module(L.device, spec, true);
-    } else {
-      get_module(L.device, spec, false);
-    }
+    const wx_launch L = launch_of(launch_);
+    prepare_module(L, select_spec(table, exprs, n_exprs, cond, L));
   });
 }
 
@@ -2936,16 +72,8 @@ wx_status wx_prepare_gather(const wx_table *table, const char *const *exprs, int
                             char *err, size_t errlen) {
   return guarded(err, errlen, [&] {
     check_gather_args(table, exprs, n_exprs, 8, 0);
-    const wx_launch L = launch_ ? *launch_ : default_launch();
-    const Spec spec = gather_spec(table, exprs, n_exprs, L);
-    int ndev = 0;
-    const bool have_gpu = hipGetDeviceCount(&ndev) == hipSuccess && ndev > L.device;
-    if (have_gpu) {
-      DevGuard g(L.device);
-      get_module(L.device, spec, true);
-    } else {
-      get_module(L.device, spec, false);
-    }
+    const wx_launch L = launch_of(launch_);
+    prepare_module(L, gather_spec(table, exprs, n_exprs, L));
   });
 }
 
@@ -3145,11 +273,7 @@ wx_status wx_fill_synthetic(void *d_ptr, int32_t dtype, int64_t n, uint64_t seed
     if (dtype < WX_INT32 || dtype > WX_FLOAT64) fail(WX_ERR_INVALID, "bad dtype");
     if (kind != 0 && kind != 1) fail(WX_ERR_INVALID, "bad kind");
     if (n == 0) return;
-    const wx_launch L = launch_ ? *launch_ : default_launch();
-    DevGuard g(L.device);
-    hipStream_t s = static_cast<hipStream_t>(L.stream);
-    auto mod = util_module(L.device, true);
-    DeviceState &d = device_state(L.device, true);
+    Op op(launch_of(launch_), util_spec());
     WxFillArgs a;
     a.out = d_ptr;
     a.n = n;
@@ -3159,99 +283,47 @@ wx_status wx_fill_synthetic(void *d_ptr, int32_t dtype, int64_t n, uint64_t seed
     a.row_base = row_base;
     a.dtype = dtype;
     a.kind = kind;
-    launch(mod->fn("wx_fill_synthetic"), grid_for(n, d.cus, 16), &a, s);
-    if (L.flags & WX_F_SYNC) WX_HIP(hipStreamSynchronize(s));
+    launch(op.mod->fn("wx_fill_synthetic"), grid_for(n, op.d.cus, 16), &a, op.s);
+    if (op.L.flags & WX_F_SYNC) WX_HIP(hipStreamSynchronize(op.s));
   });
 }
 
 wx_status wx_prepare(const wx_table *table, int32_t op, const char *expr, const char *cond, const char *aux_expr,
                      int32_t k, const wx_launch *launch_, char *src_out, size_t src_len, char *err, size_t errlen) {
   return guarded(err, errlen, [&] {
-    const wx_launch L = launch_ ? *launch_ : default_launch();
+    const wx_launch L = launch_of(launch_);
     Spec spec;
-    spec.op = op;
+    std::string more;  // UTIL: + the key/payload radix geometry's module
     if (op == WX_OP_UTIL) {
-      // no expressions
+      spec = util_spec();
+      int items = 0, block = 0;
+      more = rs_geometry(true, &items, &block, device_visible(L) ? device_state(L.device, true).arch : default_arch());
     } else {
       check_table(table);
       if (op < WX_OP_DENSE || op > WX_OP_TOPK) fail(WX_ERR_INVALID, "bad op");
       if (blank(expr)) fail(WX_ERR_INVALID, "Empty query expression");
-      spec.cols = used_columns(table, {expr, cond, aux_expr});
-      spec.expr = one_line(expr);
-      spec.cond = blank(cond) ? std::string() : one_line(cond);
-      if (op == WX_OP_GROUP) spec.key = one_line(aux_expr);
-      if (op == WX_OP_SUM || op == WX_OP_GROUP) spec.minmax = k != 0 ? 1 : 0;  // k = 1: MIN / MAX build
-      if (op == WX_OP_COMPACT) compact_geometry(spec);
-      if (op == WX_OP_TOPK) {
-        spec.select = blank(aux_expr) ? std::string() : one_line(aux_expr);
-        if (k < 1 || k > WX_TOPK_MAX) fail(WX_ERR_UNSUPPORTED, "LIMIT must be between 1 and 32");
-        spec.topk_k = k;
-        spec.topk_desc = 1;
+      if (op == WX_OP_TOPK && (k < 1 || k > WX_TOPK_MAX)) fail(WX_ERR_UNSUPPORTED, "LIMIT must be between 1 and 32");
+      // The run path's builders, with what a prepare cannot know assumed: an
+      // aligned dense output, a descending top-K.  k = 1 of SUM / GROUP: the
+      // MIN / MAX build.
+      switch (op) {
+        case WX_OP_SUM: spec = sum_spec(table, expr, cond, L, k != 0, aux_expr); break;
+        case WX_OP_GROUP: spec = group_spec(table, expr, aux_expr, cond, L, k != 0); break;
+        case WX_OP_TOPK: spec = topk_spec(table, expr, cond, aux_expr, k, 1, L); break;
+        default: spec = project_spec(table, op, expr, cond, L, true, aux_expr); break;
       }
-      bool al = true;
-      for (auto &c : spec.cols) al = al && aligned16(table->cols[c.table_index].d_ptr);
-      spec.aligned = al;
     }
-    if (op != WX_OP_UTIL) spec.custom = read_custom(&L);  // the util module never includes custom.cu
-    spec.extra = env_or("WARPDB_EXTRA_DEFINES", "");
     if (src_out && src_len) std::snprintf(src_out, src_len, "%s", spec.source().c_str());
-    int ndev = 0;
-    const bool have_gpu = hipGetDeviceCount(&ndev) == hipSuccess && ndev > L.device;
-    std::vector<Spec> specs{spec};
-    if (op == WX_OP_UTIL) {  // + the key/payload radix geometry's module
-      int items = 0, block = 0;
-      const std::string more = rs_geometry(true, &items, &block, have_gpu ? device_state(L.device, true).arch : default_arch());
-      if (!more.empty()) {
-        specs.push_back(spec);
-        specs.back().extra += more;
-      }
-    }
-    for (const Spec &sp : specs) {
-      if (have_gpu) {
-        DevGuard g(L.device);
-        get_module(L.device, sp, true);
-      } else {
-        get_module(L.device, sp, false);
-      }
-    }
+    prepare_module(L, spec);
+    if (!more.empty()) prepare_module(L, util_spec(more));
   });
 }
 
 wx_status wx_check(const wx_launch *launch_, char *err, size_t errlen) {
   return guarded(err, errlen, [&] {
-    const wx_launch L = launch_ ? *launch_ : default_launch();
-    DevGuard g(L.device);
-    Workspace &w = workspace(L.device, static_cast<hipStream_t>(L.stream));
-    OpLock op_lock(w.op_mu);
-    check_errors(w);
+    Op op(launch_of(launch_));
+    check_errors(op.w);
   });
-}
-
-// Sum and count of the unread timed launches of `device` (-1: every device).
-void timing_take(int32_t device, double *total_ms, int64_t *launches) {
-  std::vector<TimedLaunch> mine;
-  {
-    Lock lk(g_mu);
-    auto keep = std::partition(g_timed.begin(), g_timed.end(),
-                               [&](const TimedLaunch &t) { return device >= 0 && t.device != device; });
-    mine.assign(keep, g_timed.end());
-    g_timed.erase(keep, g_timed.end());
-  }
-  double tot = 0;
-  int64_t n = 0;
-  for (auto &tl : mine) {
-    DevGuard g(tl.device);
-    WX_HIP(hipEventSynchronize(tl.b));
-    float ms = 0;
-    WX_HIP(hipEventElapsedTime(&ms, tl.a, tl.b));
-    tot += ms;
-    ++n;
-    Lock lk(g_mu);
-    g_event_pool[tl.device].push_back(tl.a);
-    g_event_pool[tl.device].push_back(tl.b);
-  }
-  if (total_ms) *total_ms = tot;
-  if (launches) *launches = n;
 }
 
 wx_status wx_timing_read(double *total_ms, int64_t *launches, char *err, size_t errlen) {
@@ -3262,41 +334,9 @@ wx_status wx_timing_read_device(int32_t device, double *total_ms, int64_t *launc
   return guarded(err, errlen, [&] { timing_take(device, total_ms, launches); });
 }
 
-void wx_cache_stats(int64_t *compiles, int64_t *hits) {
-  if (compiles) *compiles = g_compiles;
-  if (hits) *hits = g_hits;
-}
+void wx_cache_stats(int64_t *compiles, int64_t *hits) { cache_stats(compiles, hits); }
 
-void wx_shutdown(void) {
-  Lock lk(g_mu);
-  for (auto &kv : g_ws) {
-    Workspace &w = *kv.second;
-    (void)hipSetDevice(w.device);
-    // every buffer the workspace allocated (a fixed list here missed the
-    // GROUP BY list / partition, exchange, row-order and fold buffers)
-    for (Buf *b : w.bufs)
-      if (b->p) (void)hipFree(b->p);
-    if (w.h_err) (void)hipHostFree(w.h_err);
-  }
-  g_ws.clear();
-  for (auto &kv : g_devices) {
-    (void)hipSetDevice(kv.first);
-    for (auto &m : kv.second.modules)
-      if (m.second->mod) (void)hipModuleUnload(m.second->mod);
-  }
-  g_devices.clear();
-  for (auto &kv : g_event_pool) {
-    (void)hipSetDevice(kv.first);
-    for (auto e : kv.second) (void)hipEventDestroy(e);
-  }
-  g_event_pool.clear();
-  for (auto &t : g_timed) {
-    (void)hipSetDevice(t.device);
-    (void)hipEventDestroy(t.a);
-    (void)hipEventDestroy(t.b);
-  }
-  g_timed.clear();
-}
+void wx_shutdown(void) { shutdown(); }
 
 int32_t wx_abi_version(void) { return WX_ABI_VERSION; }
 
