@@ -132,7 +132,6 @@ class WarpDB {
   const HostTable &host_table() const { return host_table_; }
 
  private:
-  void lower(const std::string &query, std::string &expr_c, std::string &cond_c) const;
   warpdb::ResidentShards &shards();
   Table table_;
   HostTable host_table_;

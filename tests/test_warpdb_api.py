@@ -114,6 +114,24 @@ def test_query_errors():
         pw().WarpDB(os.path.join(GOLDEN, "golden.json.bak"))
 
 
+def test_facade_refusals_table():
+    # tests/golden/facade_errors.tsv: entry point, input, the whole message of
+    # every refusal the facade raises before its first device call, with the
+    # rows that pin which of two defects wins.  tests/cpp/frontend_test.cpp
+    # reads the same table against the planner alone, without a GPU.
+    db = pw().WarpDB(TEST_CSV)
+    assert db.column_names == ["price", "quantity"] and db.num_rows == 4
+    rows = 0
+    with open(os.path.join(GOLDEN, "facade_errors.tsv")) as f:
+        for line in f:
+            entry, text, message = line.rstrip("\n").split("\t")
+            with pytest.raises(RuntimeError) as e:
+                getattr(db, entry)(text)
+            assert str(e.value) == message, (entry, text)
+            rows += 1
+    assert rows > 100
+
+
 def test_query_sql_reference_expectations():
     db = pw().WarpDB(TEST_CSV)
     assert db.query_sql("SELECT SUM(price) FROM test GROUP BY quantity ORDER BY quantity ASC") == \

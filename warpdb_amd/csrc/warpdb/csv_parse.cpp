@@ -9,6 +9,9 @@
 // cell it does not consume whole (leading blanks, '+', hex, trailing text,
 // out-of-range) is re-read with strto* so the value and the error are the
 // ones the sequential parser gives.
+//
+// CsvChunkReader (the streaming path's parser stage) cuts an input stream
+// into tables of rows_per_chunk rows and parses each with parse_csv_rows.
 #include <cerrno>
 #include <charconv>
 #include <climits>
@@ -200,6 +203,47 @@ void parse_csv_rows(const char *b, const char *e, HostTable &out, int threads) {
     for (auto &col : out.columns) std::visit([&](auto &v) { v.resize(static_cast<size_t>(old_n)); }, col.data);
     throw;
   }
+}
+
+bool CsvChunkReader::next(HostTable &chunk) {
+  while (!done_) {
+    // position just past the rows_per_chunk-th non-empty line of buf_[start_..)
+    size_t pos = start_, cut = std::string::npos;
+    int64_t rows = 0;
+    while (true) {
+      const char *b = buf_.data();
+      while (rows < rows_per_chunk_ && pos < buf_.size()) {
+        const char *nl = static_cast<const char *>(std::memchr(b + pos, '\n', buf_.size() - pos));
+        if (!nl) break;
+        const size_t len = static_cast<size_t>(nl - (b + pos));
+        if (len > 1 || (len == 1 && b[pos] != '\r')) ++rows;
+        pos = static_cast<size_t>(nl - b) + 1;
+      }
+      if (rows == rows_per_chunk_) {
+        cut = pos;
+        break;
+      }
+      if (eof_) {
+        cut = buf_.size();  // the rest, a last line without '\n' included
+        break;
+      }
+      buf_.erase(0, start_);  // keep only the unconsumed text, then read on
+      pos -= start_;
+      start_ = 0;
+      const size_t old = buf_.size();
+      buf_.resize(old + block_);
+      in_.read(&buf_[old], static_cast<std::streamsize>(block_));
+      buf_.resize(old + static_cast<size_t>(in_.gcount()));
+      eof_ = !in_;
+    }
+    chunk = HostTable();
+    for (const auto &nm : names_) chunk.columns.push_back({nm, DataType::Float32, std::vector<float>()});
+    parse_csv_rows(buf_.data() + start_, buf_.data() + cut, chunk, parse_threads());
+    start_ = cut;
+    done_ = eof_ && start_ >= buf_.size();
+    if (chunk.num_rows() > 0) return true;
+  }
+  return false;
 }
 
 }  // namespace warpdb

@@ -4,6 +4,7 @@
 
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "warpdb/csv_loader.hpp"
@@ -80,7 +81,39 @@ std::vector<float> host_result(size_t n);
 int parse_threads();  // $WARPDB_PARSE_THREADS, default hardware threads, at most 16
 void parse_csv_rows(const char *b, const char *e, HostTable &out, int threads);
 
+// Headerless CSV text cut into tables of rows_per_chunk rows (the last one
+// shorter), every column Float32 as in the reference's chunk loader
+// (src/csv_loader.cpp:186-223).  The text is read in blocks of `block` bytes
+// and each chunk is cut after its rows_per_chunk-th non-empty line with
+// memchr (line-by-line std::getline capped the streaming pipeline at
+// ≈29-41 M rows/s); a chunk's rows are parsed on parse_threads() threads.
+class CsvChunkReader {
+ public:
+  CsvChunkReader(std::istream &in, std::vector<std::string> names, int64_t rows_per_chunk,
+                 size_t block = size_t(64) << 20)
+      : in_(in), names_(std::move(names)), rows_per_chunk_(rows_per_chunk), block_(block) {}
+  // The next chunk (never empty) into `chunk`; false once the input is exhausted.
+  bool next(HostTable &chunk);
+
+ private:
+  std::istream &in_;
+  const std::vector<std::string> names_;
+  const int64_t rows_per_chunk_;
+  const size_t block_;
+  std::string buf_;   // the unconsumed text: buf_[start_..)
+  size_t start_ = 0;
+  bool eof_ = false, done_ = false;
+};
+
 wx_launch sync_launch(int device, void *stream = nullptr);
 void throw_on(wx_status st, const char *err);
+
+// One C ABI call: fn(args..., err, sizeof(err)) with the error buffer every
+// wx_* signature ends in, and throw_on of its status.
+template <typename Fn, typename... Args>
+void wx_call(Fn fn, Args &&...args) {
+  char err[8192];
+  throw_on(fn(std::forward<Args>(args)..., err, sizeof(err)), err);
+}
 
 }  // namespace warpdb

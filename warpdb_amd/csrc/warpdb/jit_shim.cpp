@@ -54,10 +54,8 @@ void jit_compile_and_launch(const std::string &expr_code, const std::string &con
                             float *d_output, int device_id) {
   WxTableView v(table);
   wx_launch L = sync_launch(device_id);
-  char err[8192];
-  throw_on(wx_project_filter(&v.table, expr_code.c_str(), condition_code.c_str(), &L, WX_MODE_DENSE, d_output,
-                             nullptr, 0, 0, nullptr, nullptr, err, sizeof(err)),
-           err);
+  wx_call(wx_project_filter, &v.table, expr_code.c_str(), condition_code.c_str(), &L, WX_MODE_DENSE, d_output, nullptr,
+          0, 0, nullptr, nullptr);
 }
 
 namespace {
@@ -115,19 +113,17 @@ void jit_group_sum(const std::string &val_expr_code, const std::string &key_expr
   }
   // the reference's outputs are float sums and an int count: converted on
   // the device, nothing but the count crosses to the host
-  throw_on(wx_cast(scr.sums.ptr, WX_FLOAT64, d_out_vals, WX_FLOAT32, groups, &L, err, sizeof(err)), err);
+  wx_call(wx_cast, scr.sums.ptr, WX_FLOAT64, d_out_vals, WX_FLOAT32, groups, &L);
   DevGuard g(device_id);
   hip_ok(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(d_count), static_cast<int>(groups), 1), "hipMemsetD32");
 }
 
 void jit_sort_pairs(int *d_keys, float *d_vals, int count, bool ascending, int device_id) {
   wx_launch L = sync_launch(device_id);
-  char err[1024];
-  throw_on(wx_sort_pairs(d_keys, d_vals, count, ascending ? 1 : 0, &L, err, sizeof(err)), err);
+  wx_call(wx_sort_pairs, d_keys, d_vals, count, ascending ? 1 : 0, &L);
 }
 
 void jit_sort_float(float *d_vals, int count, bool ascending, int device_id) {
   wx_launch L = sync_launch(device_id);
-  char err[1024];
-  throw_on(wx_sort_float(d_vals, count, ascending ? 1 : 0, &L, err, sizeof(err)), err);
+  wx_call(wx_sort_float, d_vals, count, ascending ? 1 : 0, &L);
 }

@@ -232,7 +232,6 @@ StatsMap compute_column_stats(const Table &table, const std::vector<std::string>
   StatsMap out;
   WxTableView v(table);
   wx_launch L = sync_launch(table.device);
-  char err[8192];
   for (const auto &c : table.columns) {
     if (!names.empty() && std::find(names.begin(), names.end(), c.name) == names.end()) continue;
     ColumnRange r;
@@ -244,9 +243,7 @@ StatsMap compute_column_stats(const Table &table, const std::vector<std::string>
     const std::string e = c.name + "[idx]";
     const std::string not_nan = "(" + e + " == " + e + ")";
     wx_stats st{};
-    throw_on(wx_reduce_stats(&v.table, e.c_str(), r.is_int ? "" : not_nan.c_str(), &L, nullptr, &st, err,
-                             sizeof(err)),
-             err);
+    wx_call(wx_reduce_stats, &v.table, e.c_str(), r.is_int ? "" : not_nan.c_str(), &L, nullptr, &st);
     r.null_count = table.num_rows - st.count;
     if (st.min == st.min && st.max == st.max) {
       r.min = st.min;
@@ -297,11 +294,9 @@ std::vector<float> query_optimized(const std::string &expr_part, const std::stri
   const std::string cond = (cond_ast && verdict != Verdict::AlwaysTrue) ? cond_ast->to_cuda_expr() : std::string();
   WxTableView v(table);
   wx_launch L = sync_launch(table.device);
-  char err[8192];
-  DeviceBuffer out(table.device, sizeof(float) * static_cast<size_t>(n ? n : 1));
-  throw_on(wx_project_filter(&v.table, expr.c_str(), cond.c_str(), &L, WX_MODE_DENSE_FILL,
-                             static_cast<float *>(out.ptr), nullptr, 0, 0, nullptr, nullptr, err, sizeof(err)),
-           err);
+  DeviceBuffer out(table.device, sizeof(float) * static_cast<size_t>(n));
+  wx_call(wx_project_filter, &v.table, expr.c_str(), cond.c_str(), &L, WX_MODE_DENSE_FILL,
+          static_cast<float *>(out.ptr), nullptr, 0, 0, nullptr, nullptr);
   std::vector<float> h = host_result(static_cast<size_t>(n));
   if (n) {
     DevGuard g(table.device);

@@ -1,0 +1,396 @@
+// plan.cpp -- the facade's planner (plan.hpp): validation, lowering and the
+// per-entry-point plans.  Front-end headers only, no device call.
+// Reference: src/warpdb.cpp:19-44, 204-240, 330-423.
+#include "plan.hpp"
+
+#include <cctype>
+#include <cmath>
+#include <functional>
+#include <stdexcept>
+
+namespace warpdb {
+
+void validate_ast(const ASTNode *node, const NameSet &cols) {
+  if (!node) return;
+  if (auto v = dynamic_cast<const VariableNode *>(node)) {
+    if (!cols.count(v->name)) throw std::runtime_error("Unknown column: " + v->name);
+  } else if (auto b = dynamic_cast<const BinaryOpNode *>(node)) {
+    validate_ast(b->left.get(), cols);
+    validate_ast(b->right.get(), cols);
+  } else if (auto f = dynamic_cast<const FunctionCallNode *>(node)) {
+    for (const auto &a : f->args) validate_ast(a.get(), cols);
+  } else if (auto a = dynamic_cast<const AggregationNode *>(node)) {
+    validate_ast(a->expr.get(), cols);
+  } else if (auto w = dynamic_cast<const WindowFunctionNode *>(node)) {
+    validate_ast(w->expr.get(), cols);
+    for (const auto &p : w->partition_by) validate_ast(p.get(), cols);
+    if (w->order_by) validate_ast(w->order_by->expr.get(), cols);
+  }
+}
+
+bool blank(const std::string &s) {
+  return std::all_of(s.begin(), s.end(), [](char c) { return std::isspace(static_cast<unsigned char>(c)); });
+}
+
+bool same_expr(const ASTNode *a, const ASTNode *b) { return a && b && a->to_cuda_expr() == b->to_cuda_expr(); }
+
+bool uses_minmax(const ASTNode *n) {
+  if (!n) return false;
+  if (auto a = dynamic_cast<const AggregationNode *>(n))
+    return a->agg == AggregationType::Min || a->agg == AggregationType::Max;
+  if (auto b = dynamic_cast<const BinaryOpNode *>(n)) return uses_minmax(b->left.get()) || uses_minmax(b->right.get());
+  return false;
+}
+
+std::string column_name(const ASTNode *n, size_t pos) {
+  if (auto v = dynamic_cast<const VariableNode *>(n)) return v->name;
+  if (auto a = dynamic_cast<const AggregationNode *>(n)) return a->agg_kernel() + "_" + std::to_string(pos);
+  return "expr" + std::to_string(pos);
+}
+
+QueryAST parse_sql(const std::string &sql) {
+  try {
+    return parse_query(tokenize(sql));
+  } catch (const std::exception &e) {
+    throw std::runtime_error(std::string("Failed to parse SQL: ") + e.what());
+  }
+}
+
+std::vector<std::string> result_column_names(const std::string &sql) {
+  const QueryAST ast = parse_sql(sql);
+  std::vector<std::string> names;
+  for (size_t i = 0; i < ast.select_list.size(); ++i) names.push_back(column_name(ast.select_list[i].get(), i));
+  return names;
+}
+
+void validate_clauses(const QueryAST &ast, const NameSet &cols, std::initializer_list<Clause> clauses) {
+  auto check = [&](const ASTNode *n, const char *ctx) {
+    try {
+      validate_ast(n, cols);
+    } catch (const std::exception &e) {
+      throw std::runtime_error(std::string(ctx) + ": " + e.what());
+    }
+  };
+  for (Clause c : clauses) {
+    switch (c) {
+      case Clause::Select:
+        for (const auto &e : ast.select_list) check(e.get(), "SELECT clause");
+        break;
+      case Clause::Join:
+        for (const auto &j : ast.joins) check(j.condition.get(), "JOIN condition");
+        break;
+      case Clause::Where:
+        if (ast.where) check(ast.where->get(), "WHERE clause");
+        break;
+      case Clause::GroupBy:
+        if (ast.group_by)
+          for (const auto &k : ast.group_by->keys) check(k.get(), "GROUP BY");
+        break;
+      case Clause::OrderBy:
+        if (ast.order_by) check(ast.order_by->expr.get(), "ORDER BY");
+        break;
+    }
+  }
+}
+
+namespace {
+ASTNodePtr parse_plain(const std::string &text) {
+  try {
+    return parse_expression(tokenize(text));
+  } catch (const std::exception &err) {
+    throw std::runtime_error(std::string("Failed to parse expression: ") + err.what());
+  }
+}
+
+std::string lowered_where(const QueryAST &ast) { return ast.where ? (*ast.where)->to_cuda_expr() : std::string(); }
+
+bool is_agg(const ASTNode *n) { return dynamic_cast<const AggregationNode *>(n) != nullptr; }
+bool is_window(const ASTNode *n) { return dynamic_cast<const WindowFunctionNode *>(n) != nullptr; }
+
+const char *const kTooManyItems = "a select list takes at most ";
+}  // namespace
+
+Lowered lower_query(const std::string &query, const NameSet &cols) {
+  if (query.empty()) throw std::runtime_error("Empty query expression");
+  std::string e, c;
+  split_where(query, e, c);
+  const ASTNodePtr ex = parse_plain(e);
+  validate_ast(ex.get(), cols);
+  Lowered q;
+  q.expr = ex->to_cuda_expr();
+  q.cond = lower_where(c, cols);
+  return q;
+}
+
+std::string lower_where(const std::string &where, const NameSet &cols) {
+  if (blank(where)) return {};
+  try {
+    const ASTNodePtr cx = parse_expression(tokenize(where));
+    validate_ast(cx.get(), cols);
+    return cx->to_cuda_expr();
+  } catch (const std::exception &err) {
+    throw std::runtime_error(std::string("Failed to parse WHERE clause: ") + err.what());
+  }
+}
+
+std::string lower_order_by(const std::string &order_by, const NameSet &cols) {
+  if (blank(order_by)) throw std::runtime_error("Empty ORDER BY expression");
+  try {
+    const ASTNodePtr ox = parse_expression(tokenize(order_by));
+    validate_ast(ox.get(), cols);
+    if (is_agg(ox.get())) throw std::runtime_error("aggregates are not supported here");
+    return ox->to_cuda_expr();
+  } catch (const std::exception &err) {
+    throw std::runtime_error(std::string("Failed to parse ORDER BY expression: ") + err.what());
+  }
+}
+
+SelectList lower_select_list(const std::vector<std::string> &exprs, const NameSet &cols, const char *who) {
+  if (exprs.empty()) throw std::runtime_error("Empty SELECT list");
+  if (exprs.size() > WarpDB::kMaxSelectExprs)
+    throw std::runtime_error(std::string(who) + " takes at most " + std::to_string(WarpDB::kMaxSelectExprs) +
+                             " expressions");
+  SelectList list;
+  for (size_t i = 0; i < exprs.size(); ++i) {
+    if (blank(exprs[i])) throw std::runtime_error("Empty query expression");
+    const ASTNodePtr ex = parse_plain(exprs[i]);
+    validate_ast(ex.get(), cols);
+    if (is_agg(ex.get())) throw std::runtime_error(std::string(who) + " takes plain expressions, not aggregates");
+    list.lowered.push_back(ex->to_cuda_expr());
+    list.names.push_back(column_name(ex.get(), i));
+  }
+  return list;
+}
+
+GroupPlan plan_multi_gpu_group(const std::string &sql, const NameSet &cols) {
+  const QueryAST ast = parse_sql(sql);
+  auto *agg = ast.select_list.empty() ? nullptr : dynamic_cast<const AggregationNode *>(ast.select_list[0].get());
+  if (!ast.group_by || !agg)
+    throw std::runtime_error("query_multi_gpu_group expects SELECT <agg>(expr) ... GROUP BY key");
+  if (ast.group_by->keys.size() != 1) throw std::runtime_error("GROUP BY supports one key expression");
+  if (!ast.joins.empty()) throw std::runtime_error("JOIN is not supported by the execution engine");
+  const std::string kind = agg->agg_kernel();
+  if (kind != "sum" && kind != "count" && kind != "avg")  // the shards exchange (sum, count) only
+    throw std::runtime_error("query_multi_gpu_group supports SUM / COUNT / AVG, not " + kind);
+  const ASTNode *key = ast.group_by->keys[0].get();
+  validate_ast(agg->expr.get(), cols);
+  validate_ast(key, cols);
+  if (ast.where) validate_ast(ast.where->get(), cols);
+  // SUM / COUNT / AVG all derive from the (sum, count) the shards exchange
+  GroupPlan p;
+  p.value = agg->expr->to_cuda_expr();
+  p.key = key->to_cuda_expr();
+  p.cond = lowered_where(ast);
+  return p;
+}
+
+TopkPlan plan_multi_gpu_topk(const std::string &sql, const NameSet &cols, int64_t n_rows) {
+  const QueryAST ast = parse_sql(sql);
+  if (ast.select_list.size() != 1 || ast.group_by || ast.distinct || !ast.order_by || !ast.limit)
+    throw std::runtime_error("query_multi_gpu_topk expects SELECT expr FROM t [WHERE c] ORDER BY o [DESC] LIMIT k");
+  if (is_agg(ast.select_list[0].get()))
+    throw std::runtime_error("query_multi_gpu_topk takes a plain SELECT expression");
+  if (!ast.joins.empty()) throw std::runtime_error("JOIN is not supported by the execution engine");
+  TopkPlan p;
+  p.offset = ast.offset ? ast.offset->count : 0;
+  p.limit = ast.limit->count;
+  if (p.offset < 0 || p.limit < 0) throw std::runtime_error("query_multi_gpu_topk needs OFFSET, LIMIT >= 0");
+  // nothing beyond the table: LIMIT 0 or OFFSET >= rows is an empty result
+  // (no head is gathered); otherwise offset + limit <= rows, computed without
+  // overflow, so each shard's head record holds at most the table's rows
+  p.limit = p.offset >= n_rows ? 0 : std::min(p.limit, n_rows - p.offset);
+  validate_ast(ast.select_list[0].get(), cols);
+  validate_ast(ast.order_by->expr.get(), cols);
+  if (ast.where) validate_ast(ast.where->get(), cols);
+  p.order = ast.order_by->expr->to_cuda_expr();
+  p.cond = lowered_where(ast);
+  p.select = ast.select_list[0]->to_cuda_expr();
+  p.descending = !ast.order_by->ascending;
+  return p;
+}
+
+OrderedPlan plan_sql_ordered(const std::string &sql, const NameSet &cols) {
+  const QueryAST ast = parse_sql(sql);
+  if (ast.select_list.empty()) throw std::runtime_error("Empty SELECT list");
+  if (!ast.joins.empty()) throw std::runtime_error("JOIN is not supported by query_sql_ordered");
+  if (ast.group_by) throw std::runtime_error("GROUP BY is not supported by query_sql_ordered (use query_sql_table)");
+  if (ast.distinct) throw std::runtime_error("DISTINCT is not supported by query_sql_ordered");
+  for (const auto &e : ast.select_list) {
+    if (is_window(e.get())) throw std::runtime_error("window functions are not supported by query_sql_ordered");
+    if (is_agg(e.get()))
+      throw std::runtime_error("aggregates are not supported by query_sql_ordered (plain expressions only)");
+  }
+  if (!ast.order_by) throw std::runtime_error("query_sql_ordered needs an ORDER BY clause");
+  if (is_agg(ast.order_by->expr.get()))
+    throw std::runtime_error("aggregates are not supported by query_sql_ordered (plain expressions only)");
+  validate_clauses(ast, cols, {Clause::Select, Clause::Where, Clause::OrderBy});
+  const size_t m = ast.select_list.size();
+  if (m > WarpDB::kMaxSelectExprs)
+    throw std::runtime_error(kTooManyItems + std::to_string(WarpDB::kMaxSelectExprs) + " expressions");
+  OrderedPlan p;
+  for (size_t i = 0; i < m; ++i) {
+    p.names.push_back(column_name(ast.select_list[i].get(), i));
+    p.lowered.push_back(ast.select_list[i]->to_cuda_expr());
+  }
+  p.cond = lowered_where(ast);
+  p.order = ast.order_by->expr->to_cuda_expr();
+  p.descending = !ast.order_by->ascending;
+  p.window = Window(ast);
+  return p;
+}
+
+namespace {
+// What query_sql and query_sql_table check first, in this order.
+SqlPlan checked_sql(const std::string &sql, const NameSet &cols) {
+  SqlPlan p;
+  p.ast = parse_sql(sql);
+  if (p.ast.select_list.empty()) throw std::runtime_error("Empty SELECT list");
+  validate_clauses(p.ast, cols, {Clause::Select, Clause::Join, Clause::Where, Clause::GroupBy, Clause::OrderBy});
+  if (!p.ast.joins.empty()) throw std::runtime_error("JOIN is not supported by the execution engine");
+  p.cond = lowered_where(p.ast);
+  p.window = Window(p.ast);
+  p.agg = dynamic_cast<const AggregationNode *>(p.ast.select_list[0].get());
+  return p;
+}
+
+// query_sql's own refusals of a grouped query
+void check_sql_group(const SqlPlan &p) {
+  if (!p.ast.group_by) return;
+  if (!p.agg) throw std::runtime_error("Only aggregation queries supported with GROUP BY");
+  if (p.ast.group_by->keys.size() != 1) throw std::runtime_error("GROUP BY supports one key expression");
+}
+}  // namespace
+
+SqlPlan plan_sql(const std::string &sql, const NameSet &cols) {
+  SqlPlan p = checked_sql(sql, cols);
+  check_sql_group(p);
+  return p;
+}
+
+bool grouped_minmax(const QueryAST &ast, bool select_minmax) {
+  return select_minmax || (ast.having && uses_minmax(ast.having->get())) ||
+         (ast.order_by && uses_minmax(ast.order_by->expr.get()));
+}
+
+TablePlan plan_sql_table(const std::string &sql, const NameSet &cols) {
+  TablePlan p;
+  p.sql = checked_sql(sql, cols);
+  const QueryAST &ast = p.sql.ast;
+  const size_t m = ast.select_list.size();
+  for (size_t i = 0; i < m; ++i) p.names.push_back(column_name(ast.select_list[i].get(), i));
+  for (const auto &e : ast.select_list)
+    if (is_window(e.get())) throw std::runtime_error("window functions are not supported by the execution engine");
+
+  // one item that query_sql answers whole: an aggregate, or an ordered /
+  // distinct projection (no row ids: the rows are aggregated or permuted)
+  if (m == 1 && (p.sql.agg || (!ast.group_by && (ast.order_by || ast.distinct)))) {
+    check_sql_group(p.sql);
+    p.route = TablePlan::Route::Single;
+    return p;
+  }
+
+  if (ast.group_by) {
+    if (ast.group_by->keys.size() != 1) throw std::runtime_error("GROUP BY supports one key expression");
+    if (ast.distinct) throw std::runtime_error("DISTINCT over a multi-column result is not supported");
+    const ASTNode *key = ast.group_by->keys[0].get();
+    // every item: the key, or an aggregate of the one common value expression
+    // (COUNT counts the group's rows whatever it names)
+    const ASTNode *val = nullptr, *counted = nullptr;
+    bool mm = false;
+    for (size_t i = 0; i < m; ++i) {
+      const ASTNode *item = ast.select_list[i].get();
+      if (auto a = dynamic_cast<const AggregationNode *>(item)) {
+        mm = mm || uses_minmax(a);
+        if (a->agg == AggregationType::Count) {
+          if (!counted) counted = a->expr.get();
+        } else if (!val) {
+          val = a->expr.get();
+        } else if (!same_expr(val, a->expr.get())) {
+          throw std::runtime_error("GROUP BY select list aggregates two different expressions (" +
+                                   val->to_cuda_expr() + " and " + a->expr->to_cuda_expr() + "): one is supported");
+        }
+        p.items.push_back(a->agg);
+      } else if (same_expr(item, key)) {
+        p.items.push_back(std::nullopt);
+      } else {
+        throw std::runtime_error("select item " + std::to_string(i) +
+                                 " must be the GROUP BY key or an aggregate (SUM / AVG / COUNT / MIN / MAX)");
+      }
+    }
+    p.value = val ? val : (counted ? counted : key);
+    p.minmax = grouped_minmax(ast, mm);
+    p.route = TablePlan::Route::Grouped;
+    return p;
+  }
+
+  for (const auto &e : ast.select_list)
+    if (is_agg(e.get())) throw std::runtime_error("aggregates beside other select items need GROUP BY: not supported");
+  if (ast.order_by || ast.distinct)
+    throw std::runtime_error("ORDER BY / DISTINCT over a multi-column result is not supported (row order only)");
+  if (m > WarpDB::kMaxSelectExprs)
+    throw std::runtime_error(kTooManyItems + std::to_string(WarpDB::kMaxSelectExprs) + " expressions");
+  for (const auto &e : ast.select_list) p.lowered.push_back(e->to_cuda_expr());
+  p.route = TablePlan::Route::Rows;
+  return p;
+}
+
+double GroupRun::value_of(AggregationType t, size_t i) const {
+  switch (t) {
+    case AggregationType::Sum: return sums[i];
+    case AggregationType::Avg: return sums[i] / static_cast<double>(cnts[i]);
+    case AggregationType::Count: return static_cast<double>(cnts[i]);
+    case AggregationType::Min: return mins[i];
+    case AggregationType::Max: return maxs[i];
+  }
+  return NAN;
+}
+
+void GroupRun::finish(const QueryAST &ast, const ASTNode *val, const ASTNode *key) {
+  // HAVING over the (few) aggregated groups, with the reference's
+  // comparison semantics (src/warpdb.cpp:387-423)
+  std::function<double(const ASTNode *, size_t)> having = [&](const ASTNode *n, size_t i) -> double {
+    if (auto c = dynamic_cast<const ConstantNode *>(n)) return std::stod(c->value);
+    if (auto a = dynamic_cast<const AggregationNode *>(n)) {
+      if (!same_expr(a->expr.get(), val) && a->agg != AggregationType::Count)
+        throw std::runtime_error("HAVING may only aggregate the selected expression");
+      return value_of(a->agg, i);
+    }
+    if (auto b = dynamic_cast<const BinaryOpNode *>(n)) {
+      const double l = having(b->left.get(), i), r = having(b->right.get(), i);
+      const std::string &op = b->op;
+      if (op == "+") return l + r;
+      if (op == "-") return l - r;
+      if (op == "*") return l * r;
+      if (op == "/") return l / r;
+      if (op == ">") return l > r;
+      if (op == "<") return l < r;
+      if (op == ">=") return l >= r;
+      if (op == "<=") return l <= r;
+      if (op == "==") return l == r;
+      if (op == "!=") return l != r;
+      if (op == "&&") return l != 0 && r != 0;
+      if (op == "||") return l != 0 || r != 0;
+    }
+    if (same_expr(n, key)) return keys[i];
+    throw std::runtime_error("unsupported HAVING term");
+  };
+  order.clear();
+  for (size_t i = 0; i < keys.size(); ++i)
+    if (!ast.having || having(ast.having->get(), i) != 0.0) order.push_back(i);
+  if (ast.order_by) {  // groups arrive in ascending key order
+    const ASTNode *ob = ast.order_by->expr.get();
+    auto *oagg = dynamic_cast<const AggregationNode *>(ob);
+    if (oagg) {
+      std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+        const double x = value_of(oagg->agg, a), y = value_of(oagg->agg, b);
+        return ast.order_by->ascending ? x < y : x > y;
+      });
+    } else if (same_expr(ob, key)) {
+      if (!ast.order_by->ascending) std::reverse(order.begin(), order.end());
+    } else {
+      throw std::runtime_error("ORDER BY with GROUP BY must name the key or an aggregate");
+    }
+  }
+}
+
+}  // namespace warpdb

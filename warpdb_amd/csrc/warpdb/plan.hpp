@@ -1,0 +1,165 @@
+// plan.hpp -- the planner of the WarpDB facade (not installed): everything an
+// entry point decides before its first device call.  Which inputs it refuses,
+// with which message and in which order, and what the accepted ones lower to.
+// No device call is made here, so all of it is testable without a GPU
+// (tests/cpp/frontend_test.cpp, sanitize_test.cpp); warpdb.cpp runs the plans.
+//
+// A refusal the facade raises only after a device call (it depends on the
+// groups or rows that call returned, or the call's own failure comes first)
+// is not hoisted into a plan: errors keep their place relative to device calls.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <initializer_list>
+#include <optional>
+#include <string>
+#include <unordered_set>
+#include <vector>
+
+#include "warpdb/warpdb.hpp"
+
+namespace warpdb {
+
+using NameSet = std::unordered_set<std::string>;
+
+// The column names of a Table, a HostTable, anything with .columns[i].name.
+template <typename T>
+NameSet names_of(const T &t) {
+  NameSet s;
+  for (const auto &c : t.columns) s.insert(c.name);
+  return s;
+}
+
+// Every column reference must name a table column (src/warpdb.cpp:19-44).
+void validate_ast(const ASTNode *node, const NameSet &cols);
+bool blank(const std::string &s);
+bool same_expr(const ASTNode *a, const ASTNode *b);  // both set, and the same lowered text
+bool uses_minmax(const ASTNode *n);
+// Result column name of select item `pos` (see result_column_names).
+std::string column_name(const ASTNode *n, size_t pos);
+
+// parse_query(tokenize(sql)) with the "Failed to parse SQL: " prefix.
+QueryAST parse_sql(const std::string &sql);
+
+// validate_ast over the named clauses, in the order given, each failure
+// prefixed with its clause ("SELECT clause: ", "JOIN condition: ", ...).
+enum class Clause { Select, Join, Where, GroupBy, OrderBy };
+void validate_clauses(const QueryAST &ast, const NameSet &cols, std::initializer_list<Clause> clauses);
+
+// "expr [WHERE cond]" split, parsed, validated and lowered, with the
+// reference's error prefixes; cond is empty when there is no WHERE.
+struct Lowered {
+  std::string expr, cond;
+};
+Lowered lower_query(const std::string &query, const NameSet &cols);
+// A WHERE text ("" when blank) and an ORDER BY text (never blank, no aggregate).
+std::string lower_where(const std::string &where, const NameSet &cols);
+std::string lower_order_by(const std::string &order_by, const NameSet &cols);
+// A list of plain expressions and their result names; `who` names the entry
+// point in the messages.
+struct SelectList {
+  std::vector<std::string> lowered, names;
+};
+SelectList lower_select_list(const std::vector<std::string> &exprs, const NameSet &cols, const char *who);
+
+// OFFSET / LIMIT: positions [offset, offset + limit) of a result.
+struct Window {
+  int64_t offset = 0;  // >= 0
+  int64_t limit = -1;  // < 0: to the end
+  Window() = default;
+  Window(int64_t off, int64_t lim) : offset(std::max<int64_t>(0, off)), limit(lim < 0 ? -1 : lim) {}
+  // the query's OFFSET and LIMIT clauses, negative counts taken as 0
+  explicit Window(const QueryAST &ast)
+      : Window(ast.offset ? std::max(0, ast.offset->count) : 0, ast.limit ? std::max(0, ast.limit->count) : -1) {}
+  bool limited() const { return limit >= 0; }
+  // offset + limit, saturating; -1 without a limit
+  int64_t end() const { return limit < 0 ? -1 : (limit > INT64_MAX - offset ? INT64_MAX : offset + limit); }
+  // how many leading rows of an n-row result must be computed
+  int64_t rows_needed(int64_t n) const { return limited() ? std::min(n, end()) : n; }
+  template <typename T>
+  void apply(std::vector<T> &r) const {
+    if (static_cast<uint64_t>(offset) >= r.size()) {
+      r.clear();
+      return;
+    }
+    r.erase(r.begin(), r.begin() + static_cast<long>(offset));
+    if (limited() && r.size() > static_cast<uint64_t>(limit)) r.resize(static_cast<size_t>(limit));
+  }
+  template <typename T>
+  std::vector<T> sliced(std::vector<T> r) const {
+    apply(r);
+    return r;
+  }
+};
+
+// query_multi_gpu_group: "SELECT <SUM|COUNT|AVG>(value) FROM t [WHERE cond] GROUP BY key"
+struct GroupPlan {
+  std::string value, key, cond;
+};
+GroupPlan plan_multi_gpu_group(const std::string &sql, const NameSet &cols);
+
+// query_multi_gpu_topk: limit is clamped so that offset + limit <= n_rows
+// (0: an empty result, nothing runs).
+struct TopkPlan {
+  std::string order, cond, select;
+  bool descending = false;
+  int64_t offset = 0, limit = 0;
+};
+TopkPlan plan_multi_gpu_topk(const std::string &sql, const NameSet &cols, int64_t n_rows);
+
+// query_sql_ordered
+struct OrderedPlan {
+  std::vector<std::string> names, lowered;
+  std::string cond, order;
+  bool descending = false;
+  Window window;
+};
+OrderedPlan plan_sql_ordered(const std::string &sql, const NameSet &cols);
+
+// query_sql: the validated query.  Which route it takes from here depends on
+// device results, so the executor reads the AST.
+struct SqlPlan {
+  QueryAST ast;
+  std::string cond;
+  Window window;
+  const AggregationNode *agg = nullptr;  // select item 0 when it is an aggregate (points into ast)
+};
+SqlPlan plan_sql(const std::string &sql, const NameSet &cols);
+// MIN / MAX anywhere (SELECT, HAVING, ORDER BY) selects the MIN / MAX build of a grouped query
+bool grouped_minmax(const QueryAST &ast, bool select_minmax);
+
+// query_sql_table
+struct TablePlan {
+  enum class Route {
+    Single,   // one item that query_sql answers whole (sql)
+    Grouped,  // GROUP BY key: the key and aggregates of one common value expression
+    Rows,     // plain items in row order (lowered)
+  } route = Route::Rows;
+  std::vector<std::string> names;
+  SqlPlan sql;
+  // Grouped: the common value expression (points into sql.ast), whether the
+  // MIN / MAX build is needed, and per item its aggregate (none: the key)
+  const ASTNode *value = nullptr;
+  bool minmax = false;
+  std::vector<std::optional<AggregationType>> items;
+  std::vector<std::string> lowered;  // Rows
+};
+TablePlan plan_sql_table(const std::string &sql, const NameSet &cols);
+
+// One grouped query's groups as wx_group_agg returns them (ascending key
+// order) and, after finish(), the groups HAVING keeps in result order.
+struct GroupRun {
+  std::vector<int32_t> keys;
+  std::vector<double> sums;
+  std::vector<int64_t> cnts;
+  std::vector<float> mins, maxs;  // MIN / MAX builds only
+  std::vector<size_t> order;      // the groups HAVING keeps, in result order
+  // per-group aggregate value (AggData, src/warpdb.cpp:375-385)
+  double value_of(AggregationType t, size_t i) const;
+  // HAVING, then ORDER BY, over the groups; `val` is the aggregated
+  // expression, `key` the GROUP BY key.  Its refusals are raised per group
+  // (HAVING: never with zero groups) and so only after the device call.
+  void finish(const QueryAST &ast, const ASTNode *val, const ASTNode *key);
+};
+
+}  // namespace warpdb
