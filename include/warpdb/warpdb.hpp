@@ -99,6 +99,16 @@ class WarpDB {
   // value expression, from one grouped pass; HAVING, ORDER BY, LIMIT and
   // OFFSET as in query_sql; `rows` stays empty.
   ResultTable query_sql_table(const std::string &sql);
+  // SELECT items FROM t [WHERE c] GROUP BY k [HAVING h] [ORDER BY o [ASC|DESC]]
+  // [LIMIT n] [OFFSET m]: each item is the key expression or SUM / AVG / COUNT
+  // / MIN / MAX of ANY value expression (at most kMaxSelectExprs items).  The
+  // distinct value expressions -- those HAVING and ORDER BY aggregate
+  // included, selected or not -- run four per pass over the table (one fused
+  // grouped pass: the key is read and the WHERE evaluated once for all four).
+  // HAVING, ORDER BY, LIMIT and OFFSET apply on the host over the groups;
+  // `rows` stays empty.  query_sql_table keeps refusing a select list that
+  // aggregates two different expressions.
+  ResultTable query_sql_grouped(const std::string &sql);
   // query_select as struct<one float32 child per expression, row: int64>.
   void query_arrow_select(const std::vector<std::string> &exprs, const std::string &where, ArrowArray *out_array,
                           ArrowSchema *out_schema);

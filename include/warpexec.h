@@ -25,6 +25,9 @@
  *                       src/optimizer.cpp:13-17)
  *   wx_group_agg        jit_group_sum + the per-group MIN / MAX of query_sql's
  *                       AggData (src/warpdb.cpp:375-385)
+ *   wx_group_agg_multi  the same for 2 .. 4 value expressions of one GROUP BY in
+ *                       one pass (new; query_sql aggregates one expression,
+ *                       src/warpdb.cpp:375-385)
  *   wx_group_partials,  GROUP BY over row shards: per-shard
  *   wx_group_combine    partials in an all-reduce layout and the final merge;
  *                       the reference's multi-GPU path gathers dense results
@@ -360,6 +363,48 @@ wx_status wx_group_agg(const wx_table *table, const char *val_expr, const char *
                        int64_t capacity, int32_t *d_keys, double *d_sums, int64_t *d_counts,
                        float *d_mins, float *d_maxs, int64_t *d_n_groups, int64_t *h_n_groups,
                        char *err, size_t errlen);
+
+/* wx_group_agg over several value expressions of the same GROUP BY in ONE
+ * pass: the key column is read, the condition evaluated, the window flushed
+ * and the groups ranked once for all n_vals values.  d_sums / d_mins / d_maxs
+ * are arrays of n_vals device pointers (`capacity` entries each); every
+ * pointer, and each array itself, is nullable, and what is non-null decides
+ * what the kernel carries: value j is summed when d_sums[j] is given and has
+ * its MIN / MAX tracked when d_mins[j] or d_maxs[j] is.  A value with nothing
+ * requested returns WX_ERR_INVALID.  d_keys and d_counts (the one count per
+ * group serves every value: there are no NULLs) are as in wx_group_agg, and
+ * so are the groups, the capacity rule, WX_ERR_CAPACITY with the found count
+ * in *h_n_groups, asynchrony, and the MIN / MAX semantics (NaN skipped, NaN
+ * when none qualifies, -0.0 == +0.0 -> +0.0).
+ * n_vals == 1 is wx_group_agg itself (same module, same cache entry); n_vals
+ * outside 1 .. WX_GROUP_MAX_VALUES or a blank expression returns
+ * WX_ERR_INVALID; WX_F_ROW_ORDER with n_vals >= 2 returns WX_ERR_UNSUPPORTED
+ * (one wx_group_agg call per value gives row-order sums).  The value
+ * expressions, the key and the condition together may reference at most 16
+ * columns.
+ * Routes: the LDS window + general-key hash at any capacity, as wx_group_agg's
+ * MIN / MAX builds.  With capacity > 4096 on >= 2^20 rows the call takes
+ * wx_group_sum's key-range memo for (val_exprs[0], key_expr, cond), else its
+ * 65 536-row sample (one host synchronisation), only to move the window onto
+ * a range of at most 2048 keys.  The range-partitioned kernels are not
+ * extended to several values: a wider range keeps the window + hash.
+ * Window LDS: 2048 x (4 + 8 S + 8 Q) bytes for S summed and Q MIN / MAX
+ * values; S + Q <= 4 runs two 512-thread workgroups per CU, more runs one of
+ * 1024 threads. */
+#define WX_GROUP_MAX_VALUES 4
+wx_status wx_group_agg_multi(const wx_table *table, const char *const *val_exprs, int32_t n_vals,
+                             const char *key_expr, const char *cond, const wx_launch *launch,
+                             int32_t key_window_lo, int64_t capacity, int32_t *d_keys,
+                             double *const *d_sums, int64_t *d_counts, float *const *d_mins,
+                             float *const *d_maxs, int64_t *d_n_groups, int64_t *h_n_groups,
+                             char *err, size_t errlen);
+/* Build (and cache) the module wx_group_agg_multi would use for the values
+ * whose bit is set in sum_mask (a SUM) and minmax_mask (a MIN / MAX), without
+ * launching (works without a GPU, like wx_prepare).  Every value needs a bit
+ * in one of the masks and no bit may lie at or above n_vals. */
+wx_status wx_prepare_group_multi(const wx_table *table, const char *const *val_exprs, int32_t n_vals,
+                                 uint32_t sum_mask, uint32_t minmax_mask, const char *key_expr,
+                                 const char *cond, const wx_launch *launch, char *err, size_t errlen);
 
 /* ORDER BY order_expr [DESC] LIMIT k (1 <= k <= 32) over rows where cond
  * holds; ties broken by ascending row index.  Outputs (device, nullable):

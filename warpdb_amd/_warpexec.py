@@ -61,7 +61,8 @@ def group_list_layout(cap: int):
 MODE_DENSE = 0
 MODE_DENSE_FILL = 1
 MODE_COMPACT = 2
-MAX_OUTPUTS = 4  # WX_MAX_OUTPUTS: expressions of one project_filter_multi call
+MAX_OUTPUTS = 4
+GROUP_MAX_VALUES = 4  # WX_GROUP_MAX_VALUES  # WX_MAX_OUTPUTS: expressions of one project_filter_multi call
 
 OP_DENSE, OP_COMPACT, OP_SUM, OP_GROUP, OP_TOPK, OP_UTIL = 0, 1, 2, 3, 4, 5
 
@@ -78,6 +79,8 @@ EXPORTED_SYMBOLS = (
     "wx_reduce_stats",
     "wx_group_sum",
     "wx_group_agg",
+    "wx_group_agg_multi",
+    "wx_prepare_group_multi",
     "wx_group_partials",
     "wx_group_combine",
     "wx_group_partials_slots",
@@ -167,6 +170,9 @@ def load() -> ctypes.CDLL:
         "wx_reduce_stats": [T, E, E, L, P, ctypes.POINTER(WxStats), E, S],
         "wx_group_sum": [T, E, E, E, L, I32, I64, P, P, P, P, pI64, E, S],
         "wx_group_agg": [T, E, E, E, L, I32, I64, P, P, P, P, P, P, pI64, E, S],
+        "wx_group_agg_multi": [T, ctypes.POINTER(E), I32, E, E, L, I32, I64, P, ctypes.POINTER(P), P,
+                               ctypes.POINTER(P), ctypes.POINTER(P), P, pI64, E, S],
+        "wx_prepare_group_multi": [T, ctypes.POINTER(E), I32, ctypes.c_uint32, ctypes.c_uint32, E, E, L, E, S],
         "wx_group_partials": [T, E, E, E, L, I32, P, I64, P, P, P, P, pI64, E, S],
         "wx_group_combine": [P, I32, P, P, P, I64, L, I64, P, P, P, P, pI64, E, S],
         "wx_group_partials_slots": [T, E, E, E, L, I32, P, I32, I32, I32, I64, P, P, P, P, pI64, E, S],
@@ -422,6 +428,50 @@ def group_agg(table: Table, val_expr: str, key_expr: str, cond: Optional[str], l
                           ctypes.byref(h) if want_count else None, err, len(err))
     _check(st, err)
     return h.value if want_count else None
+
+
+def _ptr_array(ptrs: Optional[Sequence[int]], n: int):
+    """n device pointers (0 = null), or None for a null array."""
+    if ptrs is None:
+        return None
+    full = list(ptrs) + [0] * (n - len(ptrs))
+    return (ctypes.c_void_p * max(1, len(full)))(*[p or None for p in full])
+
+
+def group_agg_multi(table: Table, val_exprs: Sequence[str], key_expr: str, cond: Optional[str], launch: WxLaunch,
+                    key_window_lo: int, capacity: int, d_keys: int, d_counts: int,
+                    d_sums: Optional[Sequence[int]] = None, d_mins: Optional[Sequence[int]] = None,
+                    d_maxs: Optional[Sequence[int]] = None, d_n_groups: int = 0,
+                    want_count: bool = True) -> Optional[int]:
+    """GROUP BY over len(val_exprs) value expressions in one pass: d_sums[j] /
+    d_mins[j] / d_maxs[j] (0 = not wanted; a shorter or missing list is padded
+    with nulls) receive value j's aggregates, d_keys / d_counts the groups.
+    On WX_ERR_CAPACITY the raised error carries the found count in `.count`."""
+    lib = load()
+    err = _err()
+    h = ctypes.c_int64(-1)
+    n = len(val_exprs)
+    st = lib.wx_group_agg_multi(ctypes.byref(table.c), _expr_array(val_exprs), n, _enc(key_expr), _enc(cond),
+                                ctypes.byref(launch), key_window_lo, capacity, d_keys or None,
+                                _ptr_array(d_sums, n), d_counts or None, _ptr_array(d_mins, n), _ptr_array(d_maxs, n),
+                                d_n_groups or None, ctypes.byref(h) if want_count else None, err, len(err))
+    try:
+        _check(st, err)
+    except WarpExecError as e:
+        e.count = h.value
+        raise
+    return h.value if want_count else None
+
+
+def prepare_group_multi(table: Table, val_exprs: Sequence[str], sum_mask: int, minmax_mask: int, key_expr: str,
+                        cond: Optional[str] = None, launch: Optional[WxLaunch] = None) -> None:
+    """Compile the module group_agg_multi would use for the values summed
+    (bit j of sum_mask) and min/maxed (bit j of minmax_mask); no GPU needed."""
+    lib = load()
+    err = _err()
+    L = launch or make_launch()
+    _check(lib.wx_prepare_group_multi(ctypes.byref(table.c), _expr_array(val_exprs), len(val_exprs), sum_mask,
+                                      minmax_mask, _enc(key_expr), _enc(cond), ctypes.byref(L), err, len(err)), err)
 
 
 def group_partials(table: Table, val_expr: str, key_expr: str, cond: Optional[str], launch: WxLaunch,

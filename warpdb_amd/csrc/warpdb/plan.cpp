@@ -346,15 +346,19 @@ double GroupRun::value_of(AggregationType t, size_t i) const {
 }
 
 void GroupRun::finish(const QueryAST &ast, const ASTNode *val, const ASTNode *key) {
+  finish(ast, key, [&](const AggregationNode *a, size_t i, bool having) {
+    if (having && !same_expr(a->expr.get(), val) && a->agg != AggregationType::Count)
+      throw std::runtime_error("HAVING may only aggregate the selected expression");
+    return value_of(a->agg, i);
+  });
+}
+
+void GroupRun::finish(const QueryAST &ast, const ASTNode *key, const AggValue &agg_value) {
   // HAVING over the (few) aggregated groups, with the reference's
   // comparison semantics (src/warpdb.cpp:387-423)
   std::function<double(const ASTNode *, size_t)> having = [&](const ASTNode *n, size_t i) -> double {
     if (auto c = dynamic_cast<const ConstantNode *>(n)) return std::stod(c->value);
-    if (auto a = dynamic_cast<const AggregationNode *>(n)) {
-      if (!same_expr(a->expr.get(), val) && a->agg != AggregationType::Count)
-        throw std::runtime_error("HAVING may only aggregate the selected expression");
-      return value_of(a->agg, i);
-    }
+    if (auto a = dynamic_cast<const AggregationNode *>(n)) return agg_value(a, i, true);
     if (auto b = dynamic_cast<const BinaryOpNode *>(n)) {
       const double l = having(b->left.get(), i), r = having(b->right.get(), i);
       const std::string &op = b->op;
@@ -382,7 +386,7 @@ void GroupRun::finish(const QueryAST &ast, const ASTNode *val, const ASTNode *ke
     auto *oagg = dynamic_cast<const AggregationNode *>(ob);
     if (oagg) {
       std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) {
-        const double x = value_of(oagg->agg, a), y = value_of(oagg->agg, b);
+        const double x = agg_value(oagg, a, false), y = agg_value(oagg, b, false);
         return ast.order_by->ascending ? x < y : x > y;
       });
     } else if (same_expr(ob, key)) {
@@ -391,6 +395,115 @@ void GroupRun::finish(const QueryAST &ast, const ASTNode *val, const ASTNode *ke
       throw std::runtime_error("ORDER BY with GROUP BY must name the key or an aggregate");
     }
   }
+}
+
+// ------------------------------------------------------- query_sql_grouped
+int GroupedPlan::slot_of(const AggregationNode *a) const {
+  const std::string text = a->expr->to_cuda_expr();
+  for (size_t s = 0; s < slots.size(); ++s)
+    if (slots[s].lowered == text) return static_cast<int>(s);
+  return -1;
+}
+
+std::vector<std::pair<size_t, size_t>> GroupedPlan::chunks(size_t width) const {
+  std::vector<std::pair<size_t, size_t>> c;
+  for (size_t first = 0; first < slots.size(); first += width)
+    c.emplace_back(first, std::min(width, slots.size() - first));
+  return c;
+}
+
+GroupedPlan plan_sql_grouped(const std::string &sql, const NameSet &cols) {
+  GroupedPlan p;
+  {
+    SqlPlan checked = checked_sql(sql, cols);  // plan_sql_table's first checks, in its order
+    p.ast = std::move(checked.ast);
+    p.cond = std::move(checked.cond);
+    p.window = checked.window;
+  }
+  const QueryAST &ast = p.ast;
+  const size_t m = ast.select_list.size();
+  for (size_t i = 0; i < m; ++i) p.names.push_back(column_name(ast.select_list[i].get(), i));
+  for (const auto &e : ast.select_list)
+    if (is_window(e.get())) throw std::runtime_error("window functions are not supported by the execution engine");
+  if (!ast.group_by) throw std::runtime_error("query_sql_grouped needs a GROUP BY clause");
+  if (ast.group_by->keys.size() != 1) throw std::runtime_error("GROUP BY supports one key expression");
+  if (ast.distinct) throw std::runtime_error("DISTINCT over a multi-column result is not supported");
+  if (m > WarpDB::kMaxSelectExprs)
+    throw std::runtime_error(kTooManyItems + std::to_string(WarpDB::kMaxSelectExprs) + " expressions");
+  p.key = ast.group_by->keys[0].get();
+
+  // the slot of an aggregate's expression, made on first use; COUNT takes none
+  auto use = [&](const AggregationNode *a) -> int {
+    if (a->agg == AggregationType::Count) return -1;
+    int s = p.slot_of(a);
+    if (s < 0) {
+      p.slots.push_back({a->expr->to_cuda_expr(), false, false});
+      s = static_cast<int>(p.slots.size()) - 1;
+    }
+    const bool mm = a->agg == AggregationType::Min || a->agg == AggregationType::Max;
+    p.slots[static_cast<size_t>(s)].sum = p.slots[static_cast<size_t>(s)].sum || !mm;
+    p.slots[static_cast<size_t>(s)].minmax = p.slots[static_cast<size_t>(s)].minmax || mm;
+    return s;
+  };
+  const AggregationNode *counted = nullptr;
+  for (size_t i = 0; i < m; ++i) {
+    const ASTNode *item = ast.select_list[i].get();
+    if (auto a = dynamic_cast<const AggregationNode *>(item)) {
+      if (a->agg == AggregationType::Count && !counted) counted = a;
+      p.items.push_back({a->agg, use(a)});
+    } else if (same_expr(item, p.key)) {
+      p.items.push_back({std::nullopt, -1});
+    } else {
+      throw std::runtime_error("select item " + std::to_string(i) +
+                               " must be the GROUP BY key or an aggregate (SUM / AVG / COUNT / MIN / MAX)");
+    }
+  }
+  p.selected_slots = p.slots.size();
+  // aggregates that only HAVING / ORDER BY name: hidden slots
+  std::function<void(const ASTNode *, const char *)> hidden = [&](const ASTNode *n, const char *ctx) {
+    if (auto a = dynamic_cast<const AggregationNode *>(n)) {
+      try {
+        validate_ast(a->expr.get(), cols);
+      } catch (const std::exception &e) {
+        throw std::runtime_error(std::string(ctx) + ": " + e.what());
+      }
+      if (a->agg == AggregationType::Count && !counted) counted = a;
+      use(a);
+    } else if (auto b = dynamic_cast<const BinaryOpNode *>(n)) {
+      hidden(b->left.get(), ctx);
+      hidden(b->right.get(), ctx);
+    }
+  };
+  if (ast.having) hidden(ast.having->get(), "HAVING clause");
+  if (ast.order_by) {
+    const ASTNode *ob = ast.order_by->expr.get();
+    if (!is_agg(ob) && !same_expr(ob, p.key))
+      throw std::runtime_error("ORDER BY with GROUP BY must name the key or an aggregate");
+    hidden(ob, "ORDER BY");
+  }
+  // nothing but the key and COUNTs: one summed slot to run on (what is counted, else the key)
+  if (p.slots.empty()) p.slots.push_back({(counted ? counted->expr.get() : p.key)->to_cuda_expr(), true, false});
+  return p;
+}
+
+double GroupedRun::value_of(const GroupedPlan &p, AggregationType t, int slot, size_t i) const {
+  if (t == AggregationType::Count) return static_cast<double>(run.cnts[i]);
+  if (slot < 0 || static_cast<size_t>(slot) >= slots.size()) throw std::runtime_error("aggregate without a slot");
+  const SlotData &s = slots[static_cast<size_t>(slot)];
+  switch (t) {
+    case AggregationType::Sum: return s.sums[i];
+    case AggregationType::Avg: return s.sums[i] / static_cast<double>(run.cnts[i]);
+    case AggregationType::Min: return s.mins[i];
+    case AggregationType::Max: return s.maxs[i];
+    default: break;
+  }
+  (void)p;
+  return NAN;
+}
+
+void GroupedRun::finish(const GroupedPlan &p) {
+  run.finish(p.ast, p.key,
+             [&](const AggregationNode *a, size_t i, bool) { return value_of(p, a->agg, p.slot_of(a), i); });
 }
 
 }  // namespace warpdb

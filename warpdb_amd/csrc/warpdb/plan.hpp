@@ -10,6 +10,7 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <functional>
 #include <initializer_list>
 #include <optional>
 #include <string>
@@ -160,6 +161,54 @@ struct GroupRun {
   // expression, `key` the GROUP BY key.  Its refusals are raised per group
   // (HAVING: never with zero groups) and so only after the device call.
   void finish(const QueryAST &ast, const ASTNode *val, const ASTNode *key);
+  // The same over aggregates of any expression: agg_value(a, i, having) is
+  // aggregate `a` of group i (having: asked by HAVING, else by ORDER BY).
+  using AggValue = std::function<double(const AggregationNode *a, size_t i, bool having)>;
+  void finish(const QueryAST &ast, const ASTNode *key, const AggValue &agg_value);
+};
+
+// query_sql_grouped: "SELECT items FROM t [WHERE c] GROUP BY k [HAVING h]
+// [ORDER BY o [ASC|DESC]] [LIMIT n] [OFFSET m]", each item the key or SUM /
+// AVG / COUNT / MIN / MAX of any value expression.  The value expressions are
+// deduplicated by their lowered text into slots: those of the select list
+// first, then the hidden ones only HAVING / ORDER BY aggregate.  COUNT needs
+// no slot of its own (every aggregate of a group sees the same rows); a query
+// that only counts gets one summed slot to run on.
+struct GroupedPlan {
+  QueryAST ast;
+  std::string cond;
+  Window window;
+  std::vector<std::string> names;
+  const ASTNode *key = nullptr;  // points into ast
+  struct Slot {
+    std::string lowered;
+    bool sum = false, minmax = false;  // SUM / AVG need the sum, MIN / MAX the extremes
+  };
+  std::vector<Slot> slots;
+  size_t selected_slots = 0;  // slots [0, selected_slots) come from the select list
+  struct Item {
+    std::optional<AggregationType> agg;  // none: the key
+    int slot = -1;                       // -1: the key, or a COUNT (the shared count)
+  };
+  std::vector<Item> items;
+  // the slot of an aggregate's expression (-1: none, e.g. a COUNT of an expression nothing else aggregates)
+  int slot_of(const AggregationNode *a) const;
+  // the slots in chunks of at most `width` (WX_GROUP_MAX_VALUES): [first, first + count)
+  std::vector<std::pair<size_t, size_t>> chunks(size_t width) const;
+};
+GroupedPlan plan_sql_grouped(const std::string &sql, const NameSet &cols);
+
+// The groups of a GroupedPlan: keys and counts (shared), one set of
+// aggregates per slot.  run.order after finish() as in GroupRun.
+struct GroupedRun {
+  GroupRun run;  // keys, cnts, order (its sums / mins / maxs stay empty)
+  struct SlotData {
+    std::vector<double> sums;
+    std::vector<float> mins, maxs;
+  };
+  std::vector<SlotData> slots;
+  double value_of(const GroupedPlan &p, AggregationType t, int slot, size_t i) const;
+  void finish(const GroupedPlan &p);
 };
 
 }  // namespace warpdb

@@ -196,6 +196,22 @@ PYBIND11_MODULE(pywarpdb, m) {
           "SELECT with several items (plain, or GROUP BY key + aggregates of one expression) -> "
           "(names, [float32 arrays], int64 rows; rows empty for grouped results).")
       .def(
+          "query_sql_grouped",
+          [](WarpDB &db, const std::string &sql) {
+            warpdb::ResultTable t;
+            {
+              py::gil_scoped_release nogil;
+              t = db.query_sql_grouped(sql);
+            }
+            py::list cols;
+            for (const auto &c : t.columns)
+              cols.append(py::array_t<float>(static_cast<py::ssize_t>(c.size()), c.data()));
+            return py::make_tuple(t.names, cols);
+          },
+          py::arg("sql"),
+          "SELECT key / aggregates of any value expressions ... GROUP BY key [HAVING] [ORDER BY] [LIMIT] [OFFSET] "
+          "(fused grouped passes of up to four value expressions) -> (names, [float32 arrays]).")
+      .def(
           "query_arrow_select",
           [](WarpDB &db, const std::vector<std::string> &exprs, const std::string &where) {
             return export_with<ArrowArray>(

@@ -341,6 +341,82 @@ GroupRun run_grouped(const Table &table, const QueryAST &ast, const ASTNode *val
   return run;
 }
 
+// The groups of a GroupedPlan: its slots in chunks of WX_GROUP_MAX_VALUES
+// through wx_group_agg_multi (every chunk returns the same keys and counts),
+// downloaded, then HAVING and ORDER BY on the host.  WARPDB_GROUP_ROW_ORDER=1:
+// one wx_group_agg call with WX_F_ROW_ORDER per slot instead, so that mode
+// keeps its bit-exact sums.
+warpdb::GroupedRun run_grouped_slots(const Table &table, const warpdb::GroupedPlan &p) {
+  const int dev = table.device;
+  const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(table.num_rows, 1 << 22));
+  const char *ro = std::getenv("WARPDB_GROUP_ROW_ORDER");
+  const bool row_order = ro && std::string(ro) == "1";
+  const std::string key_c = p.key->to_cuda_expr();
+  WxTableView v(table);
+  wx_launch L = sync_launch(dev);
+  if (row_order) L.flags |= WX_F_ROW_ORDER;
+  warpdb::GroupedRun r;
+  r.slots.resize(p.slots.size());
+  DeviceBuffer dk(dev, cap * 4), dc(dev, cap * 8);
+  std::vector<DeviceBuffer> ds, dmn, dmx;
+  for (int j = 0; j < WX_GROUP_MAX_VALUES; ++j) {
+    ds.emplace_back(dev, cap * 8);
+    dmn.emplace_back(dev, cap * 4);
+    dmx.emplace_back(dev, cap * 4);
+  }
+  bool first_call = true;
+  // what a call returned for slots [first, first + k): the keys and counts of
+  // the first call are the result's, every later call's must be the same
+  auto collect = [&](size_t first, size_t k, int64_t g) {
+    std::vector<int32_t> keys = download(ptr<int32_t>(dk), g, dev);
+    std::vector<int64_t> cnts = download(ptr<int64_t>(dc), g, dev);
+    if (first_call) {
+      r.run.keys = std::move(keys);
+      r.run.cnts = std::move(cnts);
+      first_call = false;
+    } else if (keys != r.run.keys || cnts != r.run.cnts) {
+      throw std::runtime_error("grouped query: the passes' groups disagree");
+    }
+    for (size_t j = 0; j < k; ++j) {
+      const auto &slot = p.slots[first + j];
+      auto &out = r.slots[first + j];
+      if (slot.sum || row_order) out.sums = download(ptr<double>(ds[j]), g, dev);
+      if (slot.minmax) {
+        out.mins = download(ptr<float>(dmn[j]), g, dev);
+        out.maxs = download(ptr<float>(dmx[j]), g, dev);
+      }
+    }
+  };
+  const size_t width = row_order ? 1 : WX_GROUP_MAX_VALUES;
+  for (const auto &[first, k] : p.chunks(width)) {
+    int64_t g = 0;
+    if (row_order) {
+      const bool mm = p.slots[first].minmax;
+      wx_call(wx_group_agg, &v.table, p.slots[first].lowered.c_str(), key_c.c_str(), p.cond.c_str(), &L, 0, cap,
+              ptr<int32_t>(dk), ptr<double>(ds[0]), ptr<int64_t>(dc), mm ? ptr<float>(dmn[0]) : nullptr,
+              mm ? ptr<float>(dmx[0]) : nullptr, nullptr, &g);
+    } else {
+      const char *ex[WX_GROUP_MAX_VALUES] = {};
+      double *sums[WX_GROUP_MAX_VALUES] = {};
+      float *mins[WX_GROUP_MAX_VALUES] = {}, *maxs[WX_GROUP_MAX_VALUES] = {};
+      for (size_t j = 0; j < k; ++j) {
+        const auto &slot = p.slots[first + j];
+        ex[j] = slot.lowered.c_str();
+        if (slot.sum) sums[j] = ptr<double>(ds[j]);
+        if (slot.minmax) {
+          mins[j] = ptr<float>(dmn[j]);
+          maxs[j] = ptr<float>(dmx[j]);
+        }
+      }
+      wx_call(wx_group_agg_multi, &v.table, ex, static_cast<int32_t>(k), key_c.c_str(), p.cond.c_str(), &L, 0, cap,
+              ptr<int32_t>(dk), sums, ptr<int64_t>(dc), mins, maxs, nullptr, &g);
+    }
+    collect(first, k, g);
+  }
+  r.finish(p);
+  return r;
+}
+
 std::vector<float> run_sql(const Table &table, const warpdb::SqlPlan &p) {
   const QueryAST &ast = p.ast;
   const std::string &cond = p.cond;
@@ -554,6 +630,22 @@ WarpDB::ResultTable WarpDB::query_sql_ordered(const std::string &sql) {
   ResultTable out;
   out.names = std::move(p.names);
   ordered_run(table_, p.lowered, p.cond, p.order, p.descending, p.window, out);
+  return out;
+}
+
+WarpDB::ResultTable WarpDB::query_sql_grouped(const std::string &sql) {
+  const warpdb::GroupedPlan p = warpdb::plan_sql_grouped(sql, names_of(table_));
+  const warpdb::GroupedRun r = run_grouped_slots(table_, p);
+  ResultTable out;
+  out.names = p.names;
+  for (const auto &item : p.items) {
+    std::vector<float> col;
+    for (size_t i : r.run.order)
+      col.push_back(item.agg ? static_cast<float>(r.value_of(p, *item.agg, item.slot, i))
+                             : static_cast<float>(r.run.keys[i]));
+    p.window.apply(col);
+    out.columns.push_back(std::move(col));
+  }
   return out;
 }
 

@@ -234,6 +234,20 @@ uint64_t gp_memo_key(const Spec &spec, const wx_table *t, const std::vector<Used
   return fnv1a(k);
 }
 
+// The general-key table of at least hcap slots (a power of two), zeroed when
+// it grows; shared by wx_group_sum and wx_group_multi.
+void ensure_group_table(Workspace &w, hipStream_t s, uint32_t hcap) {
+  if (w.g_hcap >= hcap) return;
+  ensure(w, w.g_tag, (size_t)hcap * 8, true);
+  ensure(w, w.g_sum, (size_t)hcap * 8, true);
+  ensure(w, w.g_cnt, (size_t)hcap * 8, true);
+  ensure(w, w.g_used, (size_t)hcap * 4, true);
+  WX_HIP(hipMemsetAsync(w.g_tag.p, 0, w.g_tag.bytes, s));
+  WX_HIP(hipMemsetAsync(w.g_sum.p, 0, w.g_sum.bytes, s));
+  WX_HIP(hipMemsetAsync(w.g_cnt.p, 0, w.g_cnt.bytes, s));
+  w.g_hcap = hcap;
+}
+
 void do_group_sum(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond,
                   const wx_launch *Lp, int32_t key_lo, int64_t capacity, int32_t *d_keys, double *d_sums,
                   int64_t *d_counts, int64_t *d_n_groups, int64_t *h_n_groups, float *d_mins, float *d_maxs,
@@ -256,17 +270,7 @@ void do_group_sum(const wx_table *t, const char *val_expr, const char *key_expr,
   const int gblock = gp_gblock();
   Op op(L, spec);
   // the general-key table must hold every distinct key outside the window
-  const uint32_t hcap = next_pow2(std::max<int64_t>(4096, 2 * capacity));
-  if (op.w.g_hcap < hcap) {
-    ensure(op.w, op.w.g_tag, (size_t)hcap * 8, true);
-    ensure(op.w, op.w.g_sum, (size_t)hcap * 8, true);
-    ensure(op.w, op.w.g_cnt, (size_t)hcap * 8, true);
-    ensure(op.w, op.w.g_used, (size_t)hcap * 4, true);
-    WX_HIP(hipMemsetAsync(op.w.g_tag.p, 0, op.w.g_tag.bytes, op.s));
-    WX_HIP(hipMemsetAsync(op.w.g_sum.p, 0, op.w.g_sum.bytes, op.s));
-    WX_HIP(hipMemsetAsync(op.w.g_cnt.p, 0, op.w.g_cnt.bytes, op.s));
-    op.w.g_hcap = hcap;
-  }
+  ensure_group_table(op.w, op.s, next_pow2(std::max<int64_t>(4096, 2 * capacity)));
   ensure(op.w, op.w.g_win_sum, WX_GROUP_WINDOW * 8, true);
   ensure(op.w, op.w.g_win_cnt, WX_GROUP_WINDOW * 8, true);
   if (minmax && op.w.g_mm_cap < op.w.g_hcap) {

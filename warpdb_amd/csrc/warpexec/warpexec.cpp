@@ -129,6 +129,33 @@ wx_status wx_group_sum(const wx_table *table, const char *val_expr, const char *
   });
 }
 
+wx_status wx_group_agg_multi(const wx_table *table, const char *const *val_exprs, int32_t n_vals,
+                             const char *key_expr, const char *cond, const wx_launch *launch_, int32_t key_window_lo,
+                             int64_t capacity, int32_t *d_keys, double *const *d_sums, int64_t *d_counts,
+                             float *const *d_mins, float *const *d_maxs, int64_t *d_n_groups, int64_t *h_n_groups,
+                             char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    do_group_multi(table, val_exprs, n_vals, key_expr, cond, launch_, key_window_lo, capacity, d_keys, d_sums,
+                   d_counts, d_mins, d_maxs, d_n_groups, h_n_groups);
+  });
+}
+
+wx_status wx_prepare_group_multi(const wx_table *table, const char *const *val_exprs, int32_t n_vals,
+                                 uint32_t sum_mask, uint32_t minmax_mask, const char *key_expr, const char *cond,
+                                 const wx_launch *launch_, char *err, size_t errlen) {
+  if (n_vals == 1 && val_exprs && !blank(val_exprs[0]) && !blank(key_expr) && ((sum_mask | minmax_mask) == 1u))
+    return wx_prepare(table, WX_OP_GROUP, val_exprs[0], cond, key_expr, minmax_mask ? 1 : 0, launch_, nullptr, 0, err,
+                      errlen);
+  return guarded(err, errlen, [&] {
+    check_table(table);
+    check_group_multi_exprs(val_exprs, n_vals, key_expr);
+    if ((sum_mask | minmax_mask) >> WX_GROUP_MAX_VALUES) fail(WX_ERR_INVALID, "an aggregate mask names a value beyond n_vals");
+    check_group_multi_masks(n_vals, (int)sum_mask, (int)minmax_mask);
+    const wx_launch L = launch_of(launch_);
+    prepare_module(L, group_multi_spec(table, val_exprs, n_vals, (int)sum_mask, (int)minmax_mask, key_expr, cond, L));
+  });
+}
+
 wx_status wx_group_partials(const wx_table *table, const char *val_expr, const char *key_expr, const char *cond,
                             const wx_launch *launch_, int32_t key_window_lo, double *d_window, int64_t capacity,
                             int32_t *d_keys, double *d_sums, int64_t *d_counts, int64_t *d_n_extra,

@@ -26,6 +26,7 @@
 #include "../kernels/wx_args.h"
 #include "../kernels/wx_select_args.h"
 #include "../kernels/wx_gather_args.h"
+#include "../kernels/wx_group_multi_args.h"
 
 namespace wx {
 
@@ -95,6 +96,11 @@ struct Workspace {
   Buf g_win_min, g_win_max, g_min, g_max;
   uint32_t g_mm_cap = 0;
   Buf g_sorted;  // large GROUP BY: sorted general-key entries
+  // multi-value GROUP BY (wx_group_multi.hip): the value planes of the window
+  // and of the general-key table (the counts, tags and used list are the
+  // buffers above); idle between calls (sums 0, minima ~0, maxima 0), so only
+  // a fresh allocation is filled.  gm_scratch: sums nobody asked for (n_vals == 1)
+  Buf gm_win_sum, gm_win_min, gm_win_max, gm_sum, gm_min, gm_max, gm_scratch;
   // many-key list merge (wx_group_merge_lists): merged groups, head flags,
   // per-span head counts, totals
   Buf gl_keys, gl_sums, gl_cnts, gl_head, gl_blk, gl_meta;
@@ -177,6 +183,7 @@ struct Spec {
   int dwaves = 0;  // compaction data waves per workgroup
   int gblock = 0, gunroll = 0;  // row gather: threads per workgroup, quads per thread (0 = n/a)
   int minmax = 0;        // SUM / GROUP BY builds that also track MIN / MAX
+  int gm_sums = 0, gm_mms = 0;  // multi-value GROUP BY: the values that carry a SUM / a MIN / MAX (bit j: value j)
   std::string custom;
   std::string extra;  // diagnostic -D list from $WARPDB_EXTRA_DEFINES
 
@@ -212,6 +219,10 @@ Spec topk_spec(const wx_table *t, const char *order_expr, const char *cond, cons
                int32_t desc, const wx_launch &L);
 Spec group_spec(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond, const wx_launch &L,
                 bool minmax);
+Spec group_multi_spec(const wx_table *t, const char *const *val_exprs, int32_t n_vals, int sum_mask, int mm_mask,
+                      const char *key_expr, const char *cond, const wx_launch &L);
+void check_group_multi_exprs(const char *const *val_exprs, int32_t n_vals, const char *key_expr);
+void check_group_multi_masks(int32_t n_vals, int sum_mask, int mm_mask);
 Spec select_spec(const wx_table *t, const char *const *exprs, int32_t n_exprs, const char *cond, const wx_launch &L);
 Spec gather_spec(const wx_table *t, const char *const *exprs, int32_t n_exprs, const wx_launch &L);
 Spec util_spec(const std::string &more = "");
@@ -301,6 +312,9 @@ struct KeyRange {
   int64_t lo = 0, hi = -1, passing = 0;
   int64_t span() const { return hi - lo + 1; }
 };
+uint32_t next_pow2(uint64_t v);
+int64_t gp_min_rows();
+void ensure_group_table(Workspace &w, hipStream_t s, uint32_t hcap);
 KeyRange sample_keys(const wx_table *t, const std::vector<UsedCol> &cols, Module *mod, Workspace &w, hipStream_t s,
                      bool timed);
 uint64_t gp_memo_key(const Spec &spec, const wx_table *t, const std::vector<UsedCol> &cols);
@@ -319,6 +333,12 @@ void do_group_combine_slots(const double *d_exchange, int32_t n_slots, int32_t s
 void do_group_merge_lists(const void *d_lists, int32_t n_lists, int64_t list_cap, const double *d_window,
                           int32_t key_lo, const wx_launch *Lp, int64_t capacity, int32_t *d_keys, double *d_sums,
                           int64_t *d_counts, int64_t *d_n_groups, int64_t *h_n_groups);
+
+// group_multi.cpp
+void do_group_multi(const wx_table *t, const char *const *val_exprs, int32_t n_vals, const char *key_expr,
+                    const char *cond, const wx_launch *Lp, int32_t key_lo, int64_t capacity, int32_t *d_keys,
+                    double *const *d_sums, int64_t *d_counts, float *const *d_mins, float *const *d_maxs,
+                    int64_t *d_n_groups, int64_t *h_n_groups);
 
 // group_rows.cpp
 void do_group_sum_rows(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond,
