@@ -489,6 +489,15 @@ wx_status wx_sort_float_limit(float *d_vals, int64_t count, int64_t limit, int32
                               const wx_launch *launch, char *err, size_t errlen);
 wx_status wx_sort_by_key_limit(float *d_keys, float *d_vals, int64_t count, int64_t limit,
                                int32_t ascending, const wx_launch *launch, char *err, size_t errlen);
+/* Keys per radix sort tile: of the key sorts (wx_sort_float*, with_payload
+ * 0) or of the key + payload sorts (wx_sort_by_key*, wx_sort_pairs; nonzero).
+ * The diagnostic define list may override the geometry; 0 when it is
+ * invalid.  Needs no device. */
+int32_t wx_sort_tile_keys(int32_t with_payload);
+/* Keys one workgroup of the sort's histogram pass reads per iteration (its
+ * software-pipelined loop runs where a workgroup owns two or more whole
+ * spans); 0 when the define list's override is invalid.  Needs no device. */
+int32_t wx_sort_hist_span_keys(void);
 
 /* Seeded synthetic column generator (counter-based, so every shard can
  * generate its own rows on the device):  h = splitmix64(row + seed * 0xD1B54A32D192ED03)

@@ -167,8 +167,16 @@ def test_compile_error_then_recovery():
 
 
 # ------------------------------------------------------- synthetic parity
+def compact_sizes(*sizes):
+    """`sizes` plus t - 1, t, 2t of the live single-output compaction tile
+    (wx.select_tile_rows(1), 12 288 rows; 4095 .. 4097 are an earlier tile's edges and stay)."""
+    t = wx.select_tile_rows(1)
+    assert t > 0
+    return sorted(set(sizes) | {t - 1, t, 2 * t})
+
+
 @pytest.mark.parametrize("sched", ["deep", "ticket"])
-@pytest.mark.parametrize("n", [0, 1, 5, 4095, 4096, 4097, 12289, 65536 + 3, 1_000_003])
+@pytest.mark.parametrize("n", compact_sizes(0, 1, 5, 4095, 4096, 4097, 12289, 65536 + 3, 1_000_003))
 def test_compact_c2_shape_vs_oracle(n, sched, monkeypatch):
     # both compaction schedules (the default pipeline and the one-tile-per-workgroup fallback)
     monkeypatch.setenv("WARPDB_COMPACT_SCHED", sched)
@@ -640,10 +648,18 @@ def _sort_input(n, seed):
     return v
 
 
+def radix_sizes(pairs, *sizes):
+    """`sizes` plus T - 1, T, T + 1 of the live radix tile (wx.sort_tile_keys:
+    key tiles hold 1024 x 32 = 32 768 keys, key + payload tiles 512 x 28 =
+    14 336; the fixed sizes are edges of earlier geometries and stay)."""
+    t = wx.sort_tile_keys(1 if pairs else 0)
+    assert t > 0
+    return sorted(set(sizes) | {t - 1, t, t + 1})
+
+
 # the bitonic path is a cross-check at small sizes only
-# radix tile edges: key tiles hold 512 x 32 = 16 384 keys, key + payload tiles 512 x 20 = 10 240
-@pytest.mark.parametrize("sort,n", [("radix", n) for n in (8191, 10240, 10241, 16383, 16384, 16385, 24577,
-                                                           3 * 16384 + 1, 3_000_017)]
+@pytest.mark.parametrize("sort,n", [("radix", n) for n in radix_sizes(False, 8191, 10240, 10241, 16383, 16384, 16385,
+                                                                      24577, 3 * 16384 + 1, 3_000_017)]
                          + [("bitonic", 8191)])
 def test_sort_float_stable_nan_signed_zero(n, sort, monkeypatch):
     monkeypatch.setenv("WARPDB_SORT", sort)
@@ -712,7 +728,8 @@ def test_sort_ranking_modes_agree(n, monkeypatch):
             assert np.array_equal(tv.cpu().numpy(), rows[order]), (lead, asc)
 
 
-@pytest.mark.parametrize("sort,n,data", [("radix", n, "mixed") for n in (1, 2, 8191, 16385, 3 * 16384 + 1, 1_000_003)]
+@pytest.mark.parametrize("sort,n,data", [("radix", n, "mixed")
+                                         for n in radix_sizes(False, 1, 2, 8191, 16385, 3 * 16384 + 1, 1_000_003)]
                          + [("radix", 70_001, "constant"), ("radix", 70_001, "small_ints"),
                             ("bitonic", 8191, "mixed")])
 def test_sort_float_from_column(sort, n, data, monkeypatch):
@@ -739,7 +756,7 @@ def test_sort_float_from_column(sort, n, data, monkeypatch):
         assert np.array_equal(bits(same.cpu().numpy()), bits(ref))
 
 
-@pytest.mark.parametrize("n", [10240, 10241, 12288, 12289, 2 * 10240 + 1, 100_003, 2_500_001])
+@pytest.mark.parametrize("n", radix_sizes(True, 10240, 10241, 12288, 12289, 2 * 10240 + 1, 100_003, 2_500_001))
 @pytest.mark.parametrize("span", ["narrow", "full"])
 def test_sort_pairs_radix_stable(n, span):
     # narrow keys leave three digits constant (those passes are skipped);

@@ -97,6 +97,8 @@ EXPORTED_SYMBOLS = (
     "wx_sort_by_key",
     "wx_sort_float_limit",
     "wx_sort_by_key_limit",
+    "wx_sort_tile_keys",
+    "wx_sort_hist_span_keys",
     "wx_fill_synthetic",
     "wx_prepare",
     "wx_check",
@@ -207,6 +209,10 @@ def load() -> ctypes.CDLL:
     lib.wx_select_tile_rows.restype = ctypes.c_int32
     lib.wx_gather_tile_rows.argtypes = [I32]
     lib.wx_gather_tile_rows.restype = ctypes.c_int32
+    lib.wx_sort_tile_keys.argtypes = [I32]
+    lib.wx_sort_tile_keys.restype = ctypes.c_int32
+    lib.wx_sort_hist_span_keys.argtypes = []
+    lib.wx_sort_hist_span_keys.restype = ctypes.c_int32
     lib.wx_abi_version.argtypes = []
     lib.wx_abi_version.restype = ctypes.c_int32
     _lib = lib
@@ -651,6 +657,16 @@ def sort_by_key_limit(d_keys: int, d_vals: int, count: int, limit: int, ascendin
     err = _err()
     _check(lib.wx_sort_by_key_limit(d_keys, d_vals, count, limit, 1 if ascending else 0, ctypes.byref(launch), err,
                                     len(err)), err)
+
+
+def sort_tile_keys(with_payload) -> int:
+    """Keys per radix sort tile, of the key sorts or (with_payload) of the key + payload sorts (0: invalid geometry)."""
+    return int(load().wx_sort_tile_keys(1 if with_payload else 0))
+
+
+def sort_hist_span_keys() -> int:
+    """Keys per workgroup iteration of the sort's histogram pass."""
+    return int(load().wx_sort_hist_span_keys())
 
 
 def fill_synthetic(d_ptr: int, dtype: int, n: int, seed: int, kind: int, lo: float, hi: float,

@@ -66,16 +66,13 @@ __device__ __forceinline__ wx_u32 wx_rs_key_t(wx_u32 x) {
   return ASC ? r : ~r;
 }
 
-#ifndef WX_RS_HUNROLL
-#define WX_RS_HUNROLL 4  // 16-byte loads in flight per thread (64 B): the kernel is latency-bound below that
-#endif
+// (WX_RS_HBLOCK and WX_RS_HUNROLL: wx_radix_args.h, shared with the host.)
 // (Round 1's 256-thread histogram with 8 counter copies, 1.30 ms per 1e9
 // keys against this kernel's 0.66, profiles/r02/abl_sort_hwide*.txt, was
 // removed in round 5.)
 // One 1024-thread workgroup per CU with 32 copies of every counter (128 KB):
 // lane l adds to copy l % 32, so the 32 lanes of an LDS cycle always hit 32
 // different banks and never one address -- no digit distribution conflicts.
-#define WX_RS_HBLOCK 1024
 #define WX_RS_HC 32
 // returns 1 for a float key the plain order flip would misplace (NaN, -0.0)
 template <int KIND, bool ASC>

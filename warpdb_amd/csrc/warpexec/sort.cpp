@@ -33,12 +33,18 @@ std::string rs_rank_extra(const std::string &arch) {
   return "";
 }
 
-std::string rs_geometry(bool pairs, int *items, int *block, const std::string &arch) {
+// The part of rs_geometry that needs no device: items x block of the key
+// (or key + payload) tile, the define list's overrides applied and checked.
+void rs_tile_shape(bool pairs, int *items, int *block) {
   const std::string extra = env_or("WARPDB_EXTRA_DEFINES", "");
   *items = define_value(extra, "WX_RS_ITEMS", pairs ? 28 : WX_RS_ITEMS);
   *block = define_value(extra, "WX_RS_BLOCK", pairs ? 512 : WX_RS_BLOCK);
   if (*block < 256 || *block > 1024 || *block % 64) fail(WX_ERR_INVALID, "WX_RS_BLOCK must be 256..1024, a multiple of 64");
   if (*items < 1 || *items > 64) fail(WX_ERR_INVALID, "WX_RS_ITEMS must be 1..64");
+}
+
+std::string rs_geometry(bool pairs, int *items, int *block, const std::string &arch) {
+  rs_tile_shape(pairs, items, block);
   const std::string rank = rs_rank_extra(arch);
   if (!pairs) return rank;
   return ",WX_RS_ITEMS=" + std::to_string(*items) + ",WX_RS_BLOCK=" + std::to_string(*block) +

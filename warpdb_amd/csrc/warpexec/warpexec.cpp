@@ -293,6 +293,21 @@ wx_status wx_sort_by_key_limit(float *d_keys, float *d_vals, int64_t count, int6
   });
 }
 
+int32_t wx_sort_tile_keys(int32_t with_payload) {
+  try {
+    int items = 0, block = 0;
+    rs_tile_shape(with_payload != 0, &items, &block);
+    return (int32_t)(items * block);
+  } catch (const WxError &) {
+    return 0;
+  }
+}
+
+int32_t wx_sort_hist_span_keys(void) {
+  const int unroll = define_value(env_or("WARPDB_EXTRA_DEFINES", ""), "WX_RS_HUNROLL", WX_RS_HUNROLL);
+  return unroll < 1 || unroll > 64 ? 0 : (int32_t)(WX_RS_HBLOCK * unroll * 4);
+}
+
 wx_status wx_fill_synthetic(void *d_ptr, int32_t dtype, int64_t n, uint64_t seed, int32_t kind, double lo, double hi,
                             int64_t row_base, const wx_launch *launch_, char *err, size_t errlen) {
   return guarded(err, errlen, [&] {

@@ -26,6 +26,7 @@
 #include "../kernels/wx_args.h"
 #include "../kernels/wx_select_args.h"
 #include "../kernels/wx_gather_args.h"
+#include "../kernels/wx_radix_args.h"
 #include "../kernels/wx_group_multi_args.h"
 
 namespace wx {
@@ -348,6 +349,7 @@ void do_group_sum_rows(const wx_table *t, const char *val_expr, const char *key_
 // sort.cpp
 std::shared_ptr<Module> util_module(int dev, bool load, const std::string &more = "");
 std::string rs_rank_extra(const std::string &arch);
+void rs_tile_shape(bool pairs, int *items, int *block);
 std::string rs_geometry(bool pairs, int *items, int *block, const std::string &arch);
 void bitonic_u64(int dev, wx_u64 *keys, int64_t npad, hipStream_t s);
 // the LSD radix sort; with res_k the sorted keys and payload are left
