@@ -109,6 +109,20 @@ class WarpDB {
   // `rows` stays empty.  query_sql_table keeps refusing a select list that
   // aggregates two different expressions.
   ResultTable query_sql_grouped(const std::string &sql);
+  // SELECT items FROM t [WHERE c] [LIMIT n] [OFFSET m], each item a plain
+  // expression or SUM / AVG / COUNT / MIN / MAX (x) OVER (PARTITION BY k), at
+  // least one of them a window item: one row per row WHERE keeps, in row
+  // order with the row ids, a window item holding the aggregate of the row's
+  // partition (over the rows WHERE keeps, with query_sql_grouped's float
+  // conversions).  One grouped pass, then fused compaction passes of up to
+  // four items that look the partition's aggregate up per row.  All window
+  // items share one partition key (OVER () is one partition) and aggregate at
+  // most kMaxWindowValues different expressions; ORDER BY or a frame inside
+  // OVER, GROUP BY, HAVING, DISTINCT, an outer ORDER BY and JOIN are refused.
+  static constexpr size_t kMaxWindowValues = 4;
+  ResultTable query_sql_windowed(const std::string &sql);
+  // query_sql_windowed as struct<one float32 child per item, row: int64>.
+  void query_arrow_sql_windowed(const std::string &sql, ArrowArray *out_array, ArrowSchema *out_schema);
   // query_select as struct<one float32 child per expression, row: int64>.
   void query_arrow_select(const std::vector<std::string> &exprs, const std::string &where, ArrowArray *out_array,
                           ArrowSchema *out_schema);

@@ -406,6 +406,69 @@ wx_status wx_prepare_group_multi(const wx_table *table, const char *const *val_e
                                  uint32_t sum_mask, uint32_t minmax_mask, const char *key_expr,
                                  const char *cond, const wx_launch *launch, char *err, size_t errlen);
 
+/* Window aggregates: n_exprs plain expressions and n_items window items
+ * AGG(val_expr) OVER (PARTITION BY part_expr) of the rows cond keeps, in
+ * ascending row order -- wx_project_filter_multi's result with, for a window
+ * item, the aggregate of the row's partition (over the rows cond keeps) in
+ * place of a per-row value.  d_out_vals holds n_exprs + n_items device
+ * pointers, plain expressions first, each nullable; row ids, d_count /
+ * h_count, idx_bytes and row_base behave as in wx_project_filter_multi.
+ * A window item is (float)sum for WX_WIN_SUM, (float)(sum / (double)count)
+ * for WX_WIN_AVG, (float)count for WX_WIN_COUNT and the f32 minimum / maximum
+ * of wx_group_agg for WX_WIN_MIN / WX_WIN_MAX (a COUNT counts the partition's
+ * rows whatever its val_expr names).  The partition key is (int)part_expr;
+ * "0" makes the whole result one partition.
+ * Arguments: n_items in 1 .. 16 (0 returns WX_ERR_INVALID: that call is
+ * wx_project_filter_multi); n_exprs + n_items <= WX_ORDERED_MAX_EXPRS; the
+ * items other than COUNTs name at most WX_GROUP_MAX_VALUES distinct value
+ * expressions; a blank expression or an unknown agg returns WX_ERR_INVALID;
+ * everything referenced together may name at most 16 columns;
+ * WX_F_ROW_ORDER returns WX_ERR_UNSUPPORTED.
+ * Run: one wx_group_agg_multi call over the distinct values into workspace
+ * scratch (key_window_lo and group_capacity are its key_window_lo and
+ * capacity; more partitions than group_capacity return WX_ERR_CAPACITY with
+ * the found count in the message), one small launch that turns the groups
+ * into an f32 plane per item, then one broadcast compaction per chunk of
+ * WX_MAX_OUTPUTS outputs: the first writes the row ids and the count, later
+ * ones repeat the compaction for their outputs.  Between the grouped pass
+ * and the broadcast the call synchronises the stream once, to read the group
+ * count, the first and the last key (gathered into one record on the device)
+ * and the error words: a key span of at
+ * most WX_GROUP_WINDOW_BINS takes the dense form (the planes indexed by key
+ * - first key, copied into LDS per workgroup), a wider one the search form
+ * (a binary search over the sorted keys per row).  A key that belongs to no
+ * partition (a row cond drops) yields NaN internally and is never written.
+ * With WX_F_TIME only the broadcast compactions are timed. */
+#define WX_WIN_SUM 0 /* numbering of AggregationType */
+#define WX_WIN_AVG 1
+#define WX_WIN_COUNT 2
+#define WX_WIN_MIN 3
+#define WX_WIN_MAX 4
+typedef struct wx_window_item {
+  const char *val_expr;
+  int32_t agg;
+} wx_window_item;
+wx_status wx_window_select(const wx_table *table, const char *const *exprs, int32_t n_exprs,
+                           const wx_window_item *items, int32_t n_items, const char *part_expr,
+                           const char *cond, const wx_launch *launch, int32_t key_window_lo,
+                           int64_t group_capacity, float *const *d_out_vals, void *d_out_idx,
+                           int32_t idx_bytes, int64_t row_base, int64_t *d_count, int64_t *h_count,
+                           char *err, size_t errlen);
+/* Build (and cache) the modules wx_window_select would use -- the grouped
+ * pass and every broadcast launch, in the dense (search == 0) or the search
+ * form -- without launching (works without a GPU, like wx_prepare). */
+wx_status wx_prepare_window(const wx_table *table, const char *const *exprs, int32_t n_exprs,
+                            const wx_window_item *items, int32_t n_items, const char *part_expr,
+                            const char *cond, const wx_launch *launch, int32_t search, char *err,
+                            size_t errlen);
+/* Rows per tile of one broadcast launch of n_outputs outputs (1 ..
+ * WX_MAX_OUTPUTS), n_items of them window items (1 .. n_outputs), in the
+ * dense (search == 0) or the search form; 0 when an argument is out of
+ * range.  The dense form's LDS table takes n_items x 8 KiB from the stage
+ * buffers, so its tile shrinks with n_items.  Follows WX_COMPACT_GROUPS /
+ * WX_COMPACT_DWAVES of WARPDB_EXTRA_DEFINES like wx_select_tile_rows. */
+int32_t wx_window_tile_rows(int32_t n_outputs, int32_t n_items, int32_t search);
+
 /* ORDER BY order_expr [DESC] LIMIT k (1 <= k <= 32) over rows where cond
  * holds; ties broken by ascending row index.  Outputs (device, nullable):
  * order keys, row_base + row indices, and (float)select_expr at those rows

@@ -14,7 +14,7 @@ from __future__ import annotations
 import ctypes
 import os
 from dataclasses import dataclass
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libwarpexec.so")
@@ -63,6 +63,7 @@ MODE_DENSE_FILL = 1
 MODE_COMPACT = 2
 MAX_OUTPUTS = 4
 GROUP_MAX_VALUES = 4  # WX_GROUP_MAX_VALUES  # WX_MAX_OUTPUTS: expressions of one project_filter_multi call
+WIN_SUM, WIN_AVG, WIN_COUNT, WIN_MIN, WIN_MAX = 0, 1, 2, 3, 4  # wx_window_item.agg
 
 OP_DENSE, OP_COMPACT, OP_SUM, OP_GROUP, OP_TOPK, OP_UTIL = 0, 1, 2, 3, 4, 5
 
@@ -81,6 +82,9 @@ EXPORTED_SYMBOLS = (
     "wx_group_agg",
     "wx_group_agg_multi",
     "wx_prepare_group_multi",
+    "wx_window_select",
+    "wx_prepare_window",
+    "wx_window_tile_rows",
     "wx_group_partials",
     "wx_group_combine",
     "wx_group_partials_slots",
@@ -121,6 +125,10 @@ class WxTable(ctypes.Structure):
 class WxStats(ctypes.Structure):
     _fields_ = [("sum", ctypes.c_double), ("count", ctypes.c_int64), ("min", ctypes.c_float),
                 ("max", ctypes.c_float)]
+
+
+class WxWindowItem(ctypes.Structure):
+    _fields_ = [("val_expr", ctypes.c_char_p), ("agg", ctypes.c_int32)]
 
 
 class WxLaunch(ctypes.Structure):
@@ -175,6 +183,9 @@ def load() -> ctypes.CDLL:
         "wx_group_agg_multi": [T, ctypes.POINTER(E), I32, E, E, L, I32, I64, P, ctypes.POINTER(P), P,
                                ctypes.POINTER(P), ctypes.POINTER(P), P, pI64, E, S],
         "wx_prepare_group_multi": [T, ctypes.POINTER(E), I32, ctypes.c_uint32, ctypes.c_uint32, E, E, L, E, S],
+        "wx_window_select": [T, ctypes.POINTER(E), I32, ctypes.POINTER(WxWindowItem), I32, E, E, L, I32, I64,
+                             ctypes.POINTER(P), P, I32, I64, P, pI64, E, S],
+        "wx_prepare_window": [T, ctypes.POINTER(E), I32, ctypes.POINTER(WxWindowItem), I32, E, E, L, I32, E, S],
         "wx_group_partials": [T, E, E, E, L, I32, P, I64, P, P, P, P, pI64, E, S],
         "wx_group_combine": [P, I32, P, P, P, I64, L, I64, P, P, P, P, pI64, E, S],
         "wx_group_partials_slots": [T, E, E, E, L, I32, P, I32, I32, I32, I64, P, P, P, P, pI64, E, S],
@@ -207,6 +218,8 @@ def load() -> ctypes.CDLL:
     lib.wx_shutdown.restype = None
     lib.wx_select_tile_rows.argtypes = [I32]
     lib.wx_select_tile_rows.restype = ctypes.c_int32
+    lib.wx_window_tile_rows.argtypes = [I32, I32, I32]
+    lib.wx_window_tile_rows.restype = ctypes.c_int32
     lib.wx_gather_tile_rows.argtypes = [I32]
     lib.wx_gather_tile_rows.restype = ctypes.c_int32
     lib.wx_sort_tile_keys.argtypes = [I32]
@@ -478,6 +491,48 @@ def prepare_group_multi(table: Table, val_exprs: Sequence[str], sum_mask: int, m
     L = launch or make_launch()
     _check(lib.wx_prepare_group_multi(ctypes.byref(table.c), _expr_array(val_exprs), len(val_exprs), sum_mask,
                                       minmax_mask, _enc(key_expr), _enc(cond), ctypes.byref(L), err, len(err)), err)
+
+
+def _window_items(items: Sequence[Tuple[Optional[str], int]]):
+    return (WxWindowItem * max(1, len(items)))(*[WxWindowItem(_enc(e), int(a)) for e, a in items])
+
+
+def window_select(table: Table, exprs: Sequence[str], items: Sequence[Tuple[Optional[str], int]], part_expr: str,
+                  cond: Optional[str], launch: WxLaunch, d_out_vals: Sequence[int], key_window_lo: int = 0,
+                  group_capacity: int = 4096, d_out_idx: int = 0, idx_bytes: int = 8, row_base: int = 0,
+                  d_count: int = 0, want_count: bool = False) -> Optional[int]:
+    """Plain expressions and window items (value expression, WIN_* aggregate)
+    OVER (PARTITION BY part_expr) of the rows cond keeps, in row order:
+    d_out_vals[j] (0 = not wanted) receives output j, plain expressions
+    first; a shorter list is padded with nulls."""
+    lib = load()
+    err = _err()
+    h = ctypes.c_int64(-1)
+    n_out = len(exprs) + len(items)
+    outs = list(d_out_vals) + [0] * (n_out - len(d_out_vals))
+    ptrs = (ctypes.c_void_p * max(1, len(outs)))(*[p or None for p in outs])
+    st = lib.wx_window_select(ctypes.byref(table.c), _expr_array(exprs), len(exprs), _window_items(items), len(items),
+                              _enc(part_expr), _enc(cond), ctypes.byref(launch), key_window_lo, group_capacity, ptrs,
+                              d_out_idx or None, idx_bytes, row_base, d_count or None,
+                              ctypes.byref(h) if want_count else None, err, len(err))
+    _check(st, err)
+    return h.value if want_count else None
+
+
+def prepare_window(table: Table, exprs: Sequence[str], items: Sequence[Tuple[Optional[str], int]], part_expr: str,
+                   cond: Optional[str] = None, launch: Optional[WxLaunch] = None, search: bool = False) -> None:
+    """Compile the modules window_select would use, in the dense or the search form (no GPU needed)."""
+    lib = load()
+    err = _err()
+    L = launch or make_launch()
+    _check(lib.wx_prepare_window(ctypes.byref(table.c), _expr_array(exprs), len(exprs), _window_items(items),
+                                 len(items), _enc(part_expr), _enc(cond), ctypes.byref(L), 1 if search else 0, err,
+                                 len(err)), err)
+
+
+def window_tile_rows(n_outputs: int, n_items: int, search: bool = False) -> int:
+    """Rows per tile of one broadcast launch (0: out of range)."""
+    return int(load().wx_window_tile_rows(n_outputs, n_items, int(search)))
 
 
 def group_partials(table: Table, val_expr: str, key_expr: str, cond: Optional[str], launch: WxLaunch,

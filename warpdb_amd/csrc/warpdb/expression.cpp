@@ -322,6 +322,69 @@ QueryAST parse_query(const std::vector<Token> &tokens) {
     return p;
   };
 
+  // The window of a select item whose OVER keyword is token `over` and which
+  // ends before token `p`: OVER ( [PARTITION BY e1[, e2 ...]] [ORDER BY e
+  // [ASC|DESC]] ).  The ORDER BY is kept so that a planner can refuse it.
+  auto parse_over = [&](WindowFunctionNode &w, size_t over, size_t p) {
+    const size_t open = over + 1;
+    if (open >= p || !is_op(open, "(")) throw std::runtime_error("Expected '(' after OVER" + where_at(at(open)));
+    const size_t stop = p - 1;  // the closing parenthesis
+    if (stop == open || !is_op(stop, ")")) throw std::runtime_error("Expected ')' to close OVER" + where_at(at(p)));
+    auto need_by = [&](size_t at_pos) {
+      if (at_pos >= stop || !is_kw(at_pos, "BY"))
+        throw std::runtime_error("Expected keyword 'BY'" + where_at(at(at_pos)));
+    };
+    size_t pos_w = open + 1;
+    if (pos_w < stop && is_kw(pos_w, "PARTITION")) {
+      need_by(++pos_w);
+      ++pos_w;
+      size_t keys_end = pos_w;  // a top-level ORDER ends the key list
+      for (int depth = 0; keys_end < stop && !(depth == 0 && is_kw(keys_end, "ORDER")); ++keys_end) {
+        if (is_op(keys_end, "(")) ++depth;
+        if (is_op(keys_end, ")")) --depth;
+      }
+      do {
+        size_t r = pos_w;
+        for (int depth = 0; r < keys_end && !(depth == 0 && is_op(r, ",")); ++r) {
+          if (is_op(r, "(")) ++depth;
+          if (is_op(r, ")")) --depth;
+        }
+        if (r == pos_w) throw std::runtime_error("Expected an expression after PARTITION BY" + where_at(at(pos_w)));
+        w.partition_by.push_back(parse_in_query(tokens, pos_w, r));
+        pos_w = r;
+      } while (pos_w < keys_end && is_op(pos_w++, ","));
+    }
+    if (pos_w < stop && is_kw(pos_w, "ORDER")) {
+      need_by(++pos_w);
+      ++pos_w;
+      // the key expression ends at a top-level comma, or where a word or a
+      // number follows a complete operand (ASC / DESC, a frame, a second key)
+      auto operand_end = [&](size_t p) {
+        return tokens[p].type == TokenType::Identifier || tokens[p].type == TokenType::Number || is_op(p, ")");
+      };
+      auto starts_word = [&](size_t p) {
+        if (tokens[p].type == TokenType::Keyword) return tokens[p].value != "AND" && tokens[p].value != "OR";
+        return tokens[p].type == TokenType::Identifier || tokens[p].type == TokenType::Number;
+      };
+      size_t expr_end = pos_w;
+      for (int depth = 0; expr_end < stop; ++expr_end) {
+        if (depth == 0 && (is_op(expr_end, ",") || (expr_end > pos_w && operand_end(expr_end - 1) && starts_word(expr_end))))
+          break;
+        if (is_op(expr_end, "(")) ++depth;
+        if (is_op(expr_end, ")")) --depth;
+      }
+      OrderByClause ob;
+      ob.ascending = true;
+      if (expr_end == pos_w) throw std::runtime_error("Expected an expression after ORDER BY" + where_at(at(pos_w)));
+      ob.expr = parse_in_query(tokens, pos_w, expr_end);
+      pos_w = expr_end;
+      if (pos_w < stop && (is_kw(pos_w, "ASC") || is_kw(pos_w, "DESC"))) ob.ascending = tokens[pos_w++].value == "ASC";
+      w.order_by = std::move(ob);
+    }
+    if (pos_w != stop)
+      throw std::runtime_error("Unexpected token in OVER clause: " + tokens[pos_w].value + where_at(tokens[pos_w]));
+  };
+
   QueryAST q;
   expect("SELECT");
   if (is_kw(pos, "DISTINCT")) {
@@ -349,8 +412,13 @@ QueryAST parse_query(const std::vector<Token> &tokens) {
         inner = std::make_unique<ConstantNode>("1");
       else
         inner = parse_in_query(tokens, pos + 2, over - 1);
-      if (over < p) q.select_list.push_back(std::make_unique<WindowFunctionNode>(agg, std::move(inner)));
-      else q.select_list.push_back(std::make_unique<AggregationNode>(agg, std::move(inner)));
+      if (over < p) {
+        auto w = std::make_unique<WindowFunctionNode>(agg, std::move(inner));
+        parse_over(*w, over, p);
+        q.select_list.push_back(std::move(w));
+      } else {
+        q.select_list.push_back(std::make_unique<AggregationNode>(agg, std::move(inner)));
+      }
     } else {
       q.select_list.push_back(parse_in_query(tokens, pos, p));
     }

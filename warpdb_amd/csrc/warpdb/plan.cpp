@@ -506,4 +506,72 @@ void GroupedRun::finish(const GroupedPlan &p) {
              [&](const AggregationNode *a, size_t i, bool) { return value_of(p, a->agg, p.slot_of(a), i); });
 }
 
+// ------------------------------------------------------ query_sql_windowed
+WindowedPlan plan_sql_windowed(const std::string &sql, const NameSet &cols) {
+  const QueryAST ast = parse_sql(sql);
+  if (ast.select_list.empty()) throw std::runtime_error("Empty SELECT list");
+  validate_clauses(ast, cols, {Clause::Select, Clause::Join, Clause::Where, Clause::GroupBy, Clause::OrderBy});
+  if (!ast.joins.empty()) throw std::runtime_error("JOIN is not supported by query_sql_windowed");
+  if (ast.group_by)
+    throw std::runtime_error("GROUP BY is not supported by query_sql_windowed (use query_sql_grouped)");
+  if (ast.having) throw std::runtime_error("HAVING is not supported by query_sql_windowed");
+  if (ast.distinct) throw std::runtime_error("DISTINCT is not supported by query_sql_windowed");
+  if (ast.order_by)
+    throw std::runtime_error("ORDER BY is not supported by query_sql_windowed (the result is in row order)");
+  const size_t m = ast.select_list.size();
+  std::vector<const WindowFunctionNode *> wins;
+  for (const auto &e : ast.select_list)
+    if (auto w = dynamic_cast<const WindowFunctionNode *>(e.get())) wins.push_back(w);
+  if (wins.empty())
+    throw std::runtime_error("query_sql_windowed needs a window item, AGG(x) OVER (PARTITION BY k) (use query_sql_table)");
+  for (const auto &e : ast.select_list)
+    if (is_agg(e.get()))
+      throw std::runtime_error("a plain aggregate beside window items is not supported by query_sql_windowed");
+  for (const auto *w : wins)
+    if (w->order_by)
+      throw std::runtime_error("ORDER BY inside OVER is not supported (PARTITION BY only: no running or framed "
+                               "aggregates)");
+  for (const auto *w : wins)
+    if (w->partition_by.size() > 1) throw std::runtime_error("PARTITION BY supports one key expression");
+  // OVER () and a constant key (PARTITION BY 0) name the same single partition: the key 0
+  auto partition_of = [](const WindowFunctionNode *w) {
+    if (w->partition_by.empty() || dynamic_cast<const ConstantNode *>(w->partition_by[0].get()))
+      return std::string("0");
+    return w->partition_by[0]->to_cuda_expr();
+  };
+  for (const auto *w : wins) {
+    if (!w->partition_by.empty() && (is_agg(w->partition_by[0].get()) || is_window(w->partition_by[0].get())))
+      throw std::runtime_error("PARTITION BY takes a plain expression, not an aggregate");
+    if (partition_of(w) != partition_of(wins[0]))
+      throw std::runtime_error("window items partition by two different expressions (" + partition_of(wins[0]) +
+                               " and " + partition_of(w) + "): one is supported");
+  }
+  if (m > WarpDB::kMaxSelectExprs)
+    throw std::runtime_error(kTooManyItems + std::to_string(WarpDB::kMaxSelectExprs) + " expressions");
+  // distinct value expressions: a COUNT counts the partition's rows whatever it names
+  std::vector<std::string> values;
+  for (const auto *w : wins) {
+    const std::string v = w->expr->to_cuda_expr();
+    if (w->agg != AggregationType::Count && std::find(values.begin(), values.end(), v) == values.end())
+      values.push_back(v);
+  }
+  if (values.size() > WarpDB::kMaxWindowValues)
+    throw std::runtime_error("window items aggregate " + std::to_string(values.size()) +
+                             " different expressions: at most " + std::to_string(WarpDB::kMaxWindowValues) +
+                             " are supported");
+  WindowedPlan p;
+  p.cond = lowered_where(ast);
+  p.partition = partition_of(wins[0]);
+  p.window = Window(ast);
+  for (size_t i = 0; i < m; ++i) {
+    const ASTNode *item = ast.select_list[i].get();
+    p.names.push_back(column_name(item, i));
+    if (auto w = dynamic_cast<const WindowFunctionNode *>(item)) p.items.push_back({w->expr->to_cuda_expr(), w->agg});
+    else p.plain.push_back(item->to_cuda_expr());
+  }
+  size_t next_plain = 0, next_item = p.plain.size();
+  for (size_t i = 0; i < m; ++i) p.output.push_back(is_window(ast.select_list[i].get()) ? next_item++ : next_plain++);
+  return p;
+}
+
 }  // namespace warpdb

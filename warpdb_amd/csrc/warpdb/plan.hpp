@@ -198,6 +198,26 @@ struct GroupedPlan {
 };
 GroupedPlan plan_sql_grouped(const std::string &sql, const NameSet &cols);
 
+// query_sql_windowed: "SELECT items FROM t [WHERE c] [LIMIT n] [OFFSET m]",
+// each item a plain expression or SUM / AVG / COUNT / MIN / MAX (value) OVER
+// (PARTITION BY key), at least one of them a window item and all of them over
+// the one partition key (compared by its lowering; OVER () is the key `0`,
+// one partition).  wx_window_select takes the plain expressions first, then
+// the window items: `output[i]` is where select item i lands in that order.
+struct WindowedPlan {
+  std::string cond, partition;
+  Window window;
+  std::vector<std::string> names;
+  std::vector<std::string> plain;  // lowered plain expressions, in list order
+  struct Item {
+    std::string value;  // lowered value expression
+    AggregationType agg;
+  };
+  std::vector<Item> items;  // the window items, in list order
+  std::vector<size_t> output;
+};
+WindowedPlan plan_sql_windowed(const std::string &sql, const NameSet &cols);
+
 // The groups of a GroupedPlan: keys and counts (shared), one set of
 // aggregates per slot.  run.order after finish() as in GroupRun.
 struct GroupedRun {

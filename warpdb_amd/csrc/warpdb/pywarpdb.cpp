@@ -212,6 +212,28 @@ PYBIND11_MODULE(pywarpdb, m) {
           "SELECT key / aggregates of any value expressions ... GROUP BY key [HAVING] [ORDER BY] [LIMIT] [OFFSET] "
           "(fused grouped passes of up to four value expressions) -> (names, [float32 arrays]).")
       .def(
+          "query_sql_windowed",
+          [](WarpDB &db, const std::string &sql) {
+            warpdb::ResultTable t;
+            {
+              py::gil_scoped_release nogil;
+              t = db.query_sql_windowed(sql);
+            }
+            return table_arrays(t);
+          },
+          py::arg("sql"),
+          "SELECT plain items and AGG(x) OVER (PARTITION BY k) items FROM t [WHERE c] [LIMIT n] [OFFSET m] "
+          "(one grouped pass, then fused broadcast passes of up to four items) -> "
+          "(names, [float32 arrays], int64 rows).")
+      .def(
+          "query_arrow_sql_windowed",
+          [](WarpDB &db, const std::string &sql) {
+            return export_with<ArrowArray>(
+                [&](ArrowArray *a, ArrowSchema *s) { db.query_arrow_sql_windowed(sql, a, s); }, arrow_capsules);
+          },
+          py::arg("sql"),
+          "query_sql_windowed as struct<one float32 child per item, row: int64> (Arrow C Data Interface capsules).")
+      .def(
           "query_arrow_select",
           [](WarpDB &db, const std::vector<std::string> &exprs, const std::string &where) {
             return export_with<ArrowArray>(

@@ -649,6 +649,47 @@ WarpDB::ResultTable WarpDB::query_sql_grouped(const std::string &sql) {
   return out;
 }
 
+WarpDB::ResultTable WarpDB::query_sql_windowed(const std::string &sql) {
+  const warpdb::WindowedPlan p = warpdb::plan_sql_windowed(sql, names_of(table_));
+  const int dev = table_.device;
+  const int64_t n = table_.num_rows;
+  const size_t n_plain = p.plain.size(), n_out = n_plain + p.items.size();
+  // as many partitions as the grouped queries allow groups
+  const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(n, 1 << 22));
+  std::vector<DeviceBuffer> vals;
+  std::vector<float *> dst;
+  for (size_t j = 0; j < n_out; ++j) {
+    vals.emplace_back(dev, sizeof(float) * static_cast<size_t>(n));
+    dst.push_back(ptr<float>(vals[j]));
+  }
+  std::vector<const char *> ex;
+  for (const auto &e : p.plain) ex.push_back(e.c_str());
+  std::vector<wx_window_item> items;
+  for (const auto &it : p.items) items.push_back({it.value.c_str(), static_cast<int32_t>(it.agg)});
+  DeviceBuffer idx(dev, sizeof(int64_t) * static_cast<size_t>(n));
+  WxTableView v(table_);
+  wx_launch L = sync_launch(dev);
+  int64_t count = 0;
+  wx_call(wx_window_select, &v.table, ex.data(), static_cast<int32_t>(n_plain), items.data(),
+          static_cast<int32_t>(items.size()), p.partition.c_str(), p.cond.c_str(), &L, 0, cap, dst.data(), idx.ptr, 8,
+          static_cast<int64_t>(0), nullptr, &count);
+  // row order: only the first OFFSET + LIMIT rows are downloaded
+  const int64_t keep = std::min(count, p.window.rows_needed(n));
+  ResultTable out;
+  out.names = p.names;
+  for (size_t i = 0; i < n_out; ++i) {
+    out.columns.push_back(download_result(dst[p.output[i]], keep, dev));
+    p.window.apply(out.columns.back());
+  }
+  out.rows = download(ptr<int64_t>(idx), keep, dev);
+  p.window.apply(out.rows);
+  return out;
+}
+
+void WarpDB::query_arrow_sql_windowed(const std::string &sql, ArrowArray *out_array, ArrowSchema *out_schema) {
+  export_result_table(query_sql_windowed(sql), out_array, out_schema);
+}
+
 void WarpDB::query_arrow_select_ordered(const std::vector<std::string> &exprs, const std::string &where,
                                         const std::string &order_by, bool descending, int64_t limit, int64_t offset,
                                         ArrowArray *out_array, ArrowSchema *out_schema) {

@@ -29,13 +29,14 @@ static void print_timeline(Op &op, unsigned grid, int64_t n_tiles) {
   std::fprintf(stderr, " tiles/wg %lld..%lld (us)\n", (long long)tmin, (long long)tmax);
 }
 
-// The launch the single- and the multi-output compaction share.  `c` is the
+// The launch the single- and the multi-output compaction and the window
+// broadcast (window.cpp) share.  `c` is the
 // WxCompactArgs inside `args`, the struct the kernels `deep_fn` / `ticket_fn`
 // take; the caller has set its columns and value outputs, the rest is filled
 // here.  Ends with the error check and the host count of a synchronous call.
-static void compact_launch(Op &op, const Spec &spec, const wx_table *t, WxCompactArgs &c, void *args,
-                           const char *deep_fn, const char *ticket_fn, void *d_out_idx, int32_t idx_bytes,
-                           int64_t row_base, int64_t *d_count, int64_t *h_count) {
+void compact_launch(Op &op, const Spec &spec, const wx_table *t, WxCompactArgs &c, void *args, const char *deep_fn,
+                    const char *ticket_fn, void *d_out_idx, int32_t idx_bytes, int64_t row_base, int64_t *d_count,
+                    int64_t *h_count) {
   Workspace &w = op.w;
   int64_t *count_dst = count_slot(w, w.count_tmp, d_count, h_count != nullptr);
   const int64_t tile_rows = (int64_t)spec.dwaves * 64 * 4 * spec.groups;

@@ -156,6 +156,36 @@ wx_status wx_prepare_group_multi(const wx_table *table, const char *const *val_e
   });
 }
 
+wx_status wx_window_select(const wx_table *table, const char *const *exprs, int32_t n_exprs,
+                           const wx_window_item *items, int32_t n_items, const char *part_expr, const char *cond,
+                           const wx_launch *launch_, int32_t key_window_lo, int64_t group_capacity,
+                           float *const *d_out_vals, void *d_out_idx, int32_t idx_bytes, int64_t row_base,
+                           int64_t *d_count, int64_t *h_count, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    do_window_select(table, exprs, n_exprs, items, n_items, part_expr, cond, launch_, key_window_lo, group_capacity,
+                     d_out_vals, d_out_idx, idx_bytes, row_base, d_count, h_count);
+  });
+}
+
+wx_status wx_prepare_window(const wx_table *table, const char *const *exprs, int32_t n_exprs,
+                            const wx_window_item *items, int32_t n_items, const char *part_expr, const char *cond,
+                            const wx_launch *launch_, int32_t search, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    do_prepare_window(table, exprs, n_exprs, items, n_items, part_expr, cond, launch_, search);
+  });
+}
+
+int32_t wx_window_tile_rows(int32_t n_outputs, int32_t n_items, int32_t search) {
+  if (search != 0 && search != 1) return 0;
+  try {
+    Spec spec;
+    window_geometry(spec, n_outputs, n_items, search != 0);
+    return (int32_t)(spec.dwaves * 64 * 4 * spec.groups);
+  } catch (const WxError &) {
+    return 0;
+  }
+}
+
 wx_status wx_group_partials(const wx_table *table, const char *val_expr, const char *key_expr, const char *cond,
                             const wx_launch *launch_, int32_t key_window_lo, double *d_window, int64_t capacity,
                             int32_t *d_keys, double *d_sums, int64_t *d_counts, int64_t *d_n_extra,

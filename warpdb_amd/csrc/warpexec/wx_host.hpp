@@ -25,6 +25,7 @@
 
 #include "../kernels/wx_args.h"
 #include "../kernels/wx_select_args.h"
+#include "../kernels/wx_window_args.h"
 #include "../kernels/wx_gather_args.h"
 #include "../kernels/wx_radix_args.h"
 #include "../kernels/wx_group_multi_args.h"
@@ -139,6 +140,12 @@ struct Workspace {
   // row-order folds of big groups (wx_xf_big_*): entries, chunk sums, chunk records
   Buf xf_ent, xf_approx, xf_rec;
   std::vector<int64_t> xf_host;  // the entries' host copy (outlives its asynchronous upload)
+  // window aggregates (wx_window.hip): the group pass's scratch results
+  // (keys, counts, group count; sums, minima and maxima per distinct value)
+  // and the per-item f32 planes the broadcast reads
+  Buf wn_keys, wn_cnts, wn_ng, wn_planes;
+  Buf wn_sums[WX_WIN_MAX_VALUES], wn_mins[WX_WIN_MAX_VALUES], wn_maxs[WX_WIN_MAX_VALUES];
+  int64_t wn_range[2] = {0, 0};  // landing slot of {group count, first | last key} (outlives the copy)
   Buf diag;  // WX_DIAG_TIMELINE per-workgroup times
   std::vector<Buf *> bufs;  // every buffer ensure() has allocated: wx_shutdown frees them all
 };
@@ -185,6 +192,11 @@ struct Spec {
   int gblock = 0, gunroll = 0;  // row gather: threads per workgroup, quads per thread (0 = n/a)
   int minmax = 0;        // SUM / GROUP BY builds that also track MIN / MAX
   int gm_sums = 0, gm_mms = 0;  // multi-value GROUP BY: the values that carry a SUM / a MIN / MAX (bit j: value j)
+  // window broadcast (wx_window.hip): outputs of the launch (0 = n/a), which
+  // of them are window items, dense (0) or search (1) form; win_exprs[j] is
+  // output j's plain expression (empty for a window item), `key` the partition
+  int win_nout = 0, win_mask = 0, win_search = 0;
+  std::vector<std::string> win_exprs;
   std::string custom;
   std::string extra;  // diagnostic -D list from $WARPDB_EXTRA_DEFINES
 
@@ -201,6 +213,7 @@ int define_value(const std::string &extra, const std::string &name, int dflt);
 void compact_geometry(Spec &spec);
 bool compact_ticket_sched();
 void select_geometry(Spec &spec, int nout);
+void window_geometry(Spec &spec, int nout, int n_items, bool search);
 void gather_geometry(Spec &spec, int nout);
 std::string default_arch();
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -226,6 +239,14 @@ void check_group_multi_exprs(const char *const *val_exprs, int32_t n_vals, const
 void check_group_multi_masks(int32_t n_vals, int sum_mask, int mm_mask);
 Spec select_spec(const wx_table *t, const char *const *exprs, int32_t n_exprs, const char *cond, const wx_launch &L);
 Spec gather_spec(const wx_table *t, const char *const *exprs, int32_t n_exprs, const wx_launch &L);
+// One launch of the window broadcast: n_out outputs, exprs[j] null for a
+// window item (bit j of win_mask).  The call's column limit is
+// check_window_args's.
+Spec window_spec(const wx_table *t, const char *const *exprs, int32_t n_out, int win_mask, bool search,
+                 const char *part_expr, const char *cond, const wx_launch &L);
+Spec window_table_spec();
+void check_window_args(const wx_table *t, const char *const *exprs, int32_t n_exprs, const wx_window_item *items,
+                       int32_t n_items, const char *part_expr, const char *cond);
 Spec util_spec(const std::string &more = "");
 
 // runtime.cpp
@@ -306,6 +327,17 @@ void do_project_filter_multi(const wx_table *t, const char *const *exprs, int32_
 void do_reduce_sum(const wx_table *t, const char *expr, const char *cond, const wx_launch *Lp, void *d_out,
                    double *h_sum, int64_t *h_count, bool minmax = false, wx_stats *h_stats = nullptr);
 void do_cast(const void *src, int32_t sdt, void *dst, int32_t ddt, int64_t n, const wx_launch *Lp);
+void compact_launch(Op &op, const Spec &spec, const wx_table *t, WxCompactArgs &c, void *args, const char *deep_fn,
+                    const char *ticket_fn, void *d_out_idx, int32_t idx_bytes, int64_t row_base, int64_t *d_count,
+                    int64_t *h_count);
+
+// window.cpp
+void do_window_select(const wx_table *t, const char *const *exprs, int32_t n_exprs, const wx_window_item *items,
+                      int32_t n_items, const char *part_expr, const char *cond, const wx_launch *Lp, int32_t key_lo,
+                      int64_t group_capacity, float *const *d_out_vals, void *d_out_idx, int32_t idx_bytes,
+                      int64_t row_base, int64_t *d_count, int64_t *h_count);
+void do_prepare_window(const wx_table *t, const char *const *exprs, int32_t n_exprs, const wx_window_item *items,
+                       int32_t n_items, const char *part_expr, const char *cond, const wx_launch *Lp, int32_t search);
 
 // group.cpp
 struct KeyRange {
