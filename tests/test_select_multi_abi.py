@@ -6,6 +6,8 @@ from __future__ import annotations
 
 import hashlib
 import os
+import re
+import subprocess
 
 import pytest
 
@@ -53,6 +55,7 @@ def test_tile_rows_shrink_with_outputs(monkeypatch):
     rows = [wx.select_tile_rows(m) for m in (1, 2, 3, 4)]
     assert rows[0] == 12288  # the single-output geometry is what it was
     assert rows[0] > rows[1] > rows[2] > rows[3] > 0
+    assert rows[1:] == [7680, 5376, 3840]  # as measured; the window broadcast starts from them
     for m, r in zip((2, 3, 4), rows[1:]):
         assert r % 256 == 0 and 2 * r * (4 * m + 2) <= 150 * 1024  # two stage buffers fit the LDS
     assert wx.select_tile_rows(0) == 0 and wx.select_tile_rows(5) == 0
@@ -62,6 +65,30 @@ def test_tile_rows_shrink_with_outputs(monkeypatch):
     assert wx.select_tile_rows(1) == 12288 and wx.select_tile_rows(2) == 0  # 12288 rows x 20 B do not fit
     monkeypatch.setenv("WARPDB_EXTRA_DEFINES", "WX_COMPACT_GROUPS=10,WX_COMPACT_DWAVES=3")
     assert wx.select_tile_rows(2) == 0  # a thread's keep bits (4 per quad) share one 32-bit word
+
+
+def program_text(*args):
+    """The program text of a multi-output module (tests/cpp/program_text.cpp: the code generator, no device)."""
+    r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp"), "bin/program_text"],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([os.path.join(ROOT, "tests", "cpp", "bin", "program_text"), *map(str, args)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return r.stdout
+
+
+def test_program_text_has_one_body(monkeypatch):
+    """A select module names its two kernels once each and takes their bodies from the shared source."""
+    monkeypatch.delenv("WARPDB_EXTRA_DEFINES", raising=False)
+    text = program_text("select", 2)
+    assert "#define WX_NOUT 2\n" in text
+    for hook, name in (("WX_CM_DEEP", "wx_select_compact_deep"), ("WX_CM_TICKET", "wx_select_compact_ticket")):
+        assert text.count(name) == 1 and text.count(f"#define {hook} {name}\n") == 1
+        assert len(re.findall(rf"\bvoid {hook}\(", text)) == 1
+    assert "wx_window_compact" not in text and "#define WX_WIN_" not in text and 'wx_window.hip"' not in text
+    assert text.count('#line 1 "wx_compact_multi.hip"') == 1
+    assert text.rindex("#line 1 ") == text.index('#line 1 "wx_compact_multi.hip"')  # appended last
 
 
 EXPRS = ["(f[idx] + (float)i[idx])", "(float)d[idx]", "((float)key[idx] * 2.0f)", "(f[idx] * f[idx])"]

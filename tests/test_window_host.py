@@ -10,6 +10,7 @@ import ctypes
 import hashlib
 import importlib.util
 import os
+import re
 import subprocess
 
 import pytest
@@ -201,6 +202,11 @@ def test_tile_rows(monkeypatch):
             assert wx.window_tile_rows(nout, 1, True) == wx.select_tile_rows(nout)
     assert wx.window_tile_rows(2, 2) < wx.window_tile_rows(2, 1)
     assert wx.window_tile_rows(4, 4) < wx.window_tile_rows(4, 1)
+    # every (outputs, items) of a launch, dense form; the search form is the select table's
+    dense = {1: [7680], 2: [6912, 6144], 3: [4608, 4608, 4608], 4: [3840, 3072, 3072, 3072]}
+    for nout, rows in dense.items():
+        assert [wx.window_tile_rows(nout, k) for k in range(1, nout + 1)] == rows
+        assert wx.window_tile_rows(nout, 1, True) == [7680, 7680, 5376, 3840][nout - 1]
     lib = wx.load()
     for args in ((0, 1, 0), (5, 1, 0), (2, 0, 0), (2, 3, 0), (1, 2, 0), (-1, 1, 0), (2, -1, 0), (2, 1, 2), (2, 1, -1)):
         assert lib.wx_window_tile_rows(*args) == 0, args
@@ -213,11 +219,28 @@ def test_tile_rows(monkeypatch):
     assert wx.window_tile_rows(4, 4) == 0  # does not fit beside a 32 KiB table
 
 
-def _frozen(module):
-    spec = importlib.util.spec_from_file_location(module, os.path.join(ROOT, "tests", module + ".py"))
+def _module(name):
+    spec = importlib.util.spec_from_file_location(name, os.path.join(ROOT, "tests", name + ".py"))
     m = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(m)
-    return m.FROZEN
+    return m
+
+
+def test_program_text_has_one_body(monkeypatch):
+    """A window module names its two kernels once each and takes their bodies from the shared source."""
+    monkeypatch.delenv("WARPDB_EXTRA_DEFINES", raising=False)
+    text = _module("test_select_multi_abi").program_text("window", 1, 1)
+    assert "#define WX_WIN_NOUT 2\n#define WX_WIN_MASK 2\n" in text
+    for hook, name in (("WX_CM_DEEP", "wx_window_compact_deep"), ("WX_CM_TICKET", "wx_window_compact_ticket")):
+        assert text.count(name) == 1 and text.count(f"#define {hook} {name}\n") == 1
+        assert len(re.findall(rf"\bvoid {hook}\(", text)) == 1
+    assert "wx_select_compact" not in text and "#define WX_NOUT" not in text and "wx_select.hip\"" not in text
+    assert text.count('#line 1 "wx_compact_multi.hip"') == 1
+    assert text.rindex("#line 1 ") == text.index('#line 1 "wx_compact_multi.hip"')  # appended last
+
+
+def _frozen(module):
+    return _module(module).FROZEN
 
 
 @pytest.mark.parametrize("module", ["test_select_multi_abi", "test_group_multi_host"])

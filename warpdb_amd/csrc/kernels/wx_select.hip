@@ -1,312 +1,21 @@
-// wx_select.hip -- multi-output ordered compaction (multi-column SELECT)
-// (appended after wx_compact.hip in a WX_OP_COMPACT module whose prelude
-// defines WX_NOUT; it reuses that file's tile macros, status words,
-// wx_lookback and wx_retire unchanged)
+// wx_select.hip -- multi-column SELECT: the hooks of the multi-output ordered
+// compaction (appended after wx_compact.hip in a WX_OP_COMPACT module whose
+// prelude defines WX_NOUT; wx_compact_multi.hip, appended after it, holds the
+// kernels and says what each hook is)
 
 // ===========================================================================
 #if WX_OP == WX_OP_COMPACT && defined(WX_NOUT)
 // WX_NOUT expressions (WX_EXPR, WX_EXPR1 .. WX_EXPR3) of one filtered result
-// in one pass: the columns are loaded once, the WHERE is evaluated once, the
-// passing rows are ranked once and one look-back chain resolves the tile's
-// offset; each passing row stages WX_NOUT values and one tile-local row
-// offset, and every output array is written with the head / aligned 16-byte
-// nontemporal body / tail pattern of wx_project_compact_deep.  Semantics are
-// WX_MODE_COMPACT's: out_val[j][k] = static_cast<float>(expression j) of the
-// k-th passing row in ascending row order, nothing written at k >= count.
-#if WX_NOUT < 1 || WX_NOUT > WX_SELECT_MAX_OUT
-#error "WX_NOUT must be between 1 and 4"
-#endif
-#if WX_COMPACT_GROUPS > 8
-#error "at most 8 row quads per thread: a thread's keep bits share one 32-bit word"
-#endif
-#if WX_NOUT > 1
-#define WX_SEL_EVAL1(V) V[1][wx_g][wx_e] = static_cast<float>(WX_EXPR1);
-#else
-#define WX_SEL_EVAL1(V)
-#endif
-#if WX_NOUT > 2
-#define WX_SEL_EVAL2(V) V[2][wx_g][wx_e] = static_cast<float>(WX_EXPR2);
-#else
-#define WX_SEL_EVAL2(V)
-#endif
-#if WX_NOUT > 3
-#define WX_SEL_EVAL3(V) V[3][wx_g][wx_e] = static_cast<float>(WX_EXPR3);
-#else
-#define WX_SEL_EVAL3(V)
-#endif
-#define WX_SEL_EVAL(V)                             \
-  V[0][wx_g][wx_e] = static_cast<float>(WX_EXPR);  \
-  WX_SEL_EVAL1(V) WX_SEL_EVAL2(V) WX_SEL_EVAL3(V)
-
-// The pipelined kernel: wx_project_compact_deep's schedule (iteration k
-// evaluates and ranks t_k and issues t_{k+1}'s loads; the control wave
-// publishes t_k, takes the ticket of iteration k + 2 and resolves t_{k-1}
-// while the data waves write t_{k-2} out of LDS and stage t_k), with
-// 2 x WX_TILE x (4 * WX_NOUT + 2) B of stage buffers.
-extern "C" __global__ __launch_bounds__(WX_CBLOCK, 1) void wx_select_compact_deep(WxSelectArgs wx_s) {
-  const WxCompactArgs &wx_a = wx_s.c;
-  const wx_u64 wx_E = (wx_u64)wx_a.epoch << WX_EPOCH_SHIFT;
-  __shared__ wx_u32 s_cnt[WX_DWAVES][WX_GROUPS];
-  __shared__ float s_val[2][WX_NOUT][WX_TILE];
-  __shared__ unsigned short s_off[2][WX_TILE];
-  __shared__ wx_i64 s_excl[2];
-  __shared__ wx_i64 s_tiles[4];
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const bool control = wave == WX_DWAVES;
-  const int wx_dt = tid;
-  if (tid == 0) {
-    const wx_i64 t0 = (wx_i64)__hip_atomic_fetch_add(&wx_a.ctrs[0], 2ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    s_tiles[0] = t0;
-    s_tiles[1] = t0 + 1;
-  }
-  __syncthreads();
-  wx_i64 tile = s_tiles[0];
-  wx_i64 tile1 = -1, tile2 = -1;   // tiles of iterations k - 1 and k - 2
-  wx_u32 tot1 = 0, tot2 = 0;       // their passing counts
-  WX_COLS(WX_DECL_TILE_IN)
-  if (!control && tile < wx_a.n_tiles) {
-    const wx_i64 wx_tb = tile * WX_TILE;
-#pragma unroll
-    for (int wx_g = 0; wx_g < WX_GROUPS; ++wx_g) { WX_COLS(WX_LOAD_TILE_IN) }
-  }
-  for (int k = 0;; ++k) {
-    const bool have = tile < wx_a.n_tiles;
-    const bool have1 = k >= 1 && tile1 < wx_a.n_tiles;
-    const bool have2 = k >= 2 && tile2 < wx_a.n_tiles;
-    if (!have && !have1 && !have2) break;
-    const wx_i64 next_tile = s_tiles[(k + 1) & 3];
-    const wx_i64 tile_base = tile * WX_TILE;
-    const int cur = k & 1;  // t_k is staged in buffer cur, t_{k-2} is read from it first
-    wx_u32 wx_kb = 0;
-    float wx_val[WX_NOUT][WX_GROUPS][4];
-    wx_u32 lane_pre[WX_GROUPS];
-    // phase 1 (data): evaluate t_k, issue t_{k+1}'s loads, rank t_k
-    if (!control && have) {
-      const wx_u32 wx_rows = (wx_u32)(wx_a.n_rows - tile_base < WX_TILE ? wx_a.n_rows - tile_base : WX_TILE);
-#pragma unroll
-      for (int wx_g = 0; wx_g < WX_GROUPS; ++wx_g) {
-#pragma unroll
-        for (int wx_e = 0; wx_e < 4; ++wx_e) {
-          WX_COLS(WX_BIND_TILE_IN)
-          const wx_u32 wx_lrow = (wx_u32)(wx_g * (WX_DTHREADS * 4) + wx_dt * 4 + wx_e);
-          const wx_i64 idx = tile_base + wx_lrow;
-          (void)idx;
-          bool wx_k = wx_lrow < wx_rows;
-          wx_k = wx_k && WX_EVAL_COND();
-          wx_kb |= (wx_k ? 1u : 0u) << (wx_g * 4 + wx_e);
-          WX_SEL_EVAL(wx_val)
-        }
-      }
-      if (next_tile < wx_a.n_tiles) {
-        const wx_i64 wx_tb = next_tile * WX_TILE;
-#pragma unroll
-        for (int wx_g = 0; wx_g < WX_GROUPS; ++wx_g) { WX_COLS(WX_LOAD_TILE_IN) }
-      }
-#pragma unroll
-      for (int g = 0; g < WX_GROUPS; ++g) {
-        wx_u32 pre = 0, tot = 0;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const wx_u64 m = __builtin_amdgcn_ballot_w64(((wx_kb >> (g * 4 + e)) & 1u) != 0u);
-          pre += wx::lanes_below(m);
-          tot += (wx_u32)__builtin_popcountll(m);
-        }
-        lane_pre[g] = pre;
-        if (lane == 0) s_cnt[wave][g] = tot;
-      }
-    }
-    __syncthreads();
-    // phase 2: control publishes t_k's aggregate and fetches the tile of
-    // iteration k + 2; data waves write t_{k-2} out of buffer cur
-    wx_u32 block_total = 0;
-    wx_u32 grp_base[WX_GROUPS];
-    if (have) { WX_BASES(s_cnt) }
-    if (control) {
-      if (lane == 0) {
-        if (have) wx::st_agent(&wx_a.status[tile], wx_E | (tile == 0 ? WX_FLAG_P : WX_FLAG_A) | (wx_u64)block_total);
-        s_tiles[(k + 2) & 3] = next_tile < wx_a.n_tiles
-                                   ? (wx_i64)__hip_atomic_fetch_add(&wx_a.ctrs[0], 1ull, __ATOMIC_RELAXED,
-                                                                    __HIP_MEMORY_SCOPE_AGENT)
-                                   : wx_a.n_tiles;
-      }
-    } else if (have2) {
-      // write t_{k-2}'s passing rows at the offset resolved in iteration k - 1:
-      // positions [excl, end) of every output, of which [b0, b1) is the
-      // 16-byte body (b0 on a 32-element boundary, b1 - b0 a multiple of 4)
-      const wx_i64 excl = s_excl[cur];
-      const wx_i64 prev_base = wx_a.row_base + tile2 * WX_TILE;
-      const unsigned short *so = s_off[cur];
-      const wx_i64 end = excl + (wx_i64)tot2;
-      wx_i64 b0 = (excl + 31) & ~(wx_i64)31;
-      if (b0 > end) b0 = end;
-      const wx_i64 b1 = b0 + ((end - b0) & ~(wx_i64)3);
-      const int n_head = (int)(b0 - excl), n_edge = n_head + (int)(end - b1);
-      for (int j = wx_dt; j < n_edge; j += WX_DTHREADS) {
-        const wx_i64 pos = j < n_head ? excl + j : b1 + (j - n_head);
-        const int i = (int)(pos - excl);
-#pragma unroll
-        for (int o = 0; o < WX_NOUT; ++o)
-          if (wx_s.out_val[o]) wx_s.out_val[o][pos] = s_val[cur][o][i];
-        if (wx_a.out_idx) {
-          const wx_i64 gi = prev_base + so[i];
-          if (wx_a.idx64) static_cast<wx_i64 *>(wx_a.out_idx)[pos] = gi;
-          else static_cast<int *>(wx_a.out_idx)[pos] = (int)gi;
-        }
-      }
-      for (wx_i64 q = b0 + 4 * (wx_i64)wx_dt; q < b1; q += 4 * (wx_i64)WX_DTHREADS) {
-        const int i = (int)(q - excl);
-#pragma unroll
-        for (int o = 0; o < WX_NOUT; ++o) {
-          if (wx_s.out_val[o]) {
-            typedef float v4f __attribute__((ext_vector_type(4)));
-            const float *sv = s_val[cur][o];
-            const v4f v = {sv[i], sv[i + 1], sv[i + 2], sv[i + 3]};
-            wx::st_sel<WX_DEEP_NT_STORE>(reinterpret_cast<v4f *>(wx_s.out_val[o] + q), v);
-          }
-        }
-        if (wx_a.out_idx) {
-          const wx_u32 o0 = so[i], o1 = so[i + 1], o2 = so[i + 2], o3 = so[i + 3];
-          if (wx_a.idx64) {
-            typedef long long v2l __attribute__((ext_vector_type(2)));
-            wx_i64 *o = static_cast<wx_i64 *>(wx_a.out_idx) + q;
-            const v2l x = {(long long)(prev_base + o0), (long long)(prev_base + o1)};
-            const v2l y = {(long long)(prev_base + o2), (long long)(prev_base + o3)};
-            wx::st_sel<WX_DEEP_NT_STORE>(reinterpret_cast<v2l *>(o), x);
-            wx::st_sel<WX_DEEP_NT_STORE>(reinterpret_cast<v2l *>(o + 2), y);
-          } else {
-            typedef int v4i __attribute__((ext_vector_type(4)));
-            const unsigned base = (unsigned)prev_base;
-            const v4i x = {(int)(base + o0), (int)(base + o1), (int)(base + o2), (int)(base + o3)};
-            wx::st_sel<WX_DEEP_NT_STORE>(reinterpret_cast<v4i *>(static_cast<int *>(wx_a.out_idx) + q), x);
-          }
-        }
-      }
-    }
-    __syncthreads();
-    // phase 3: data waves stage t_k into buffer cur; the control wave
-    // resolves t_{k-1}'s offset (published one iteration ago)
-    if (control) {
-      if (have1) {
-        wx_i64 excl = 0;
-        if (tile1 > 0) {
-          excl = wx_lookback(wx_a, tile1);
-          if (lane == 0) wx::st_agent(&wx_a.status[tile1], wx_E | WX_FLAG_P | (wx_u64)(excl + tot1));
-        }
-        if (lane == 0) {
-          s_excl[cur ^ 1] = excl;  // read when t_{k-1} is written, in iteration k + 1
-          if (tile1 == wx_a.n_tiles - 1 && wx_a.count_out) *wx_a.count_out = excl + tot1;
-        }
-      }
-    } else if (have) {
-#pragma unroll
-      for (int g = 0; g < WX_GROUPS; ++g) {
-        wx_u32 pos = grp_base[g] + lane_pre[g];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if ((wx_kb >> (g * 4 + e)) & 1u) {
-#pragma unroll
-            for (int o = 0; o < WX_NOUT; ++o) s_val[cur][o][pos] = wx_val[o][g][e];
-            s_off[cur][pos] = (unsigned short)(g * (WX_DTHREADS * 4) + wx_dt * 4 + e);
-            ++pos;
-          }
-        }
-      }
-    }
-    tile2 = tile1;
-    tot2 = tot1;
-    tile1 = tile;
-    tot1 = have ? block_total : 0u;
-    tile = next_tile;
-  }
-  if (tid == 0) wx_retire(wx_a.ctrs);
-}
-
-// One tile per workgroup, taken from a ticket counter (robust fallback,
-// WARPDB_COMPACT_SCHED=ticket): no LDS staging, each lane writes its own
-// passing rows.
-extern "C" __global__ __launch_bounds__(WX_DTHREADS) void wx_select_compact_ticket(WxSelectArgs wx_s) {
-  const WxCompactArgs &wx_a = wx_s.c;
-  const wx_u64 wx_E = (wx_u64)wx_a.epoch << WX_EPOCH_SHIFT;
-  __shared__ wx_u32 s_cnt[WX_DWAVES][WX_GROUPS];
-  __shared__ wx_i64 s_excl;
-  __shared__ wx_u32 s_tile;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int wx_dt = tid;
-  if (tid == 0)
-    s_tile = (wx_u32)__hip_atomic_fetch_add(&wx_a.ctrs[0], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  __syncthreads();
-  const wx_i64 tile = s_tile;
-  const wx_i64 tile_base = tile * WX_TILE;
-  WX_COLS(WX_DECL_TILE_IN)
-  {
-    const wx_i64 wx_tb = tile_base;
-#pragma unroll
-    for (int wx_g = 0; wx_g < WX_GROUPS; ++wx_g) { WX_COLS(WX_LOAD_TILE_IN) }
-  }
-  bool wx_keep[WX_GROUPS][4];
-  float wx_val[WX_NOUT][WX_GROUPS][4];
-  wx_u32 lane_pre[WX_GROUPS];
-#pragma unroll
-  for (int wx_g = 0; wx_g < WX_GROUPS; ++wx_g) {
-#pragma unroll
-    for (int wx_e = 0; wx_e < 4; ++wx_e) {
-      WX_COLS(WX_BIND_TILE_IN)
-      const wx_i64 idx = tile_base + (wx_i64)wx_g * (WX_DTHREADS * 4) + (wx_i64)wx_dt * 4 + wx_e;
-      bool wx_k = idx < wx_a.n_rows;
-      wx_k = wx_k && WX_EVAL_COND();
-      wx_keep[wx_g][wx_e] = wx_k;
-      WX_SEL_EVAL(wx_val)
-    }
-  }
-#pragma unroll
-  for (int g = 0; g < WX_GROUPS; ++g) {
-    wx_u32 pre = 0, tot = 0;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const wx_u64 m = __builtin_amdgcn_ballot_w64(wx_keep[g][e]);
-      pre += wx::lanes_below(m);
-      tot += (wx_u32)__builtin_popcountll(m);
-    }
-    lane_pre[g] = pre;
-    if (lane == 0) s_cnt[wave][g] = tot;
-  }
-  __syncthreads();
-  wx_u32 block_total = 0;
-  wx_u32 grp_base[WX_GROUPS];
-  WX_BASES(s_cnt)
-  if (wave == 0) {
-    wx_i64 excl = 0;
-    if (tile == 0) {
-      if (lane == 0) wx::st_agent(&wx_a.status[0], wx_E | WX_FLAG_P | (wx_u64)block_total);
-    } else {
-      if (lane == 0) wx::st_agent(&wx_a.status[tile], wx_E | WX_FLAG_A | (wx_u64)block_total);
-      excl = wx_lookback(wx_a, tile);
-      if (lane == 0) wx::st_agent(&wx_a.status[tile], wx_E | WX_FLAG_P | (wx_u64)(excl + block_total));
-    }
-    if (lane == 0) s_excl = excl;
-  }
-  __syncthreads();
-  const wx_i64 excl = s_excl;
-#pragma unroll
-  for (int g = 0; g < WX_GROUPS; ++g) {
-    const wx_i64 r0 = tile_base + (wx_i64)g * (WX_DTHREADS * 4) + (wx_i64)tid * 4;
-    wx_i64 pos = excl + grp_base[g] + lane_pre[g];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      if (wx_keep[g][e]) {
-#pragma unroll
-        for (int o = 0; o < WX_NOUT; ++o)
-          if (wx_s.out_val[o]) wx_s.out_val[o][pos] = wx_val[o][g][e];
-        if (wx_a.out_idx) {
-          const wx_i64 gi = wx_a.row_base + r0 + e;
-          if (wx_a.idx64) static_cast<wx_i64 *>(wx_a.out_idx)[pos] = gi;
-          else static_cast<int *>(wx_a.out_idx)[pos] = (int)gi;
-        }
-        ++pos;
-      }
-    }
-  }
-  if (tid == 0 && tile == wx_a.n_tiles - 1 && wx_a.count_out) *wx_a.count_out = excl + block_total;
-  if (tid == 0) wx_retire(wx_a.ctrs);
-}
+// in one pass, out_val[j][k] = static_cast<float>(expression j) of the k-th
+// passing row: the plain case of the shared kernels -- no window output, so
+// no key, no table in LDS and nothing to set up.
+#define WX_CM_NOUT WX_NOUT
+#define WX_CM_ARGS WxSelectArgs
+#define WX_CM_MASK 0
+#define WX_CM_ROW()
+#define WX_CM_SETUP()
+#define WX_CM_LDS
+#define WX_CM_FILL_LDS(NTHREADS)
+#define WX_CM_DEEP wx_select_compact_deep
+#define WX_CM_TICKET wx_select_compact_ticket
 #endif

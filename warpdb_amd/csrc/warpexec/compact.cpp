@@ -1,5 +1,6 @@
 // compact.cpp -- dense and compacting projection (wx_dense.hip,
-// wx_compact.hip), the multi-output compaction (wx_select.hip), SUM
+// wx_compact.hip), the multi-output compaction (wx_select.hip,
+// wx_compact_multi.hip), SUM
 // (wx_sum.hip) and the type cast.
 #include "wx_host.hpp"
 
@@ -105,10 +106,7 @@ void do_project_filter(const wx_table *t, const char *expr, const char *cond, co
   const wx_launch L = launch_of(Lp);
   if (blank(expr)) fail(WX_ERR_INVALID, "Empty query expression");
   if (mode < WX_MODE_DENSE || mode > WX_MODE_COMPACT) fail(WX_ERR_INVALID, "unknown mode");
-  if (mode == WX_MODE_COMPACT && d_out_idx && idx_bytes != 4 && idx_bytes != 8)
-    fail(WX_ERR_INVALID, "idx_bytes must be 4 or 8");
-  if (mode == WX_MODE_COMPACT && d_out_idx && idx_bytes == 4 && row_base + t->n_rows > INT32_MAX)
-    fail(WX_ERR_INVALID, "row indices exceed int32; use idx_bytes = 8");
+  if (mode == WX_MODE_COMPACT) check_row_ids(t, d_out_idx, idx_bytes, row_base);
   if (mode != WX_MODE_COMPACT && !d_out_vals && t->n_rows) fail(WX_ERR_INVALID, "null output buffer");
   // No WHERE and no row indices wanted: every row passes in order, so the
   // compacted values are the dense projection (no ballots, no look-back)
@@ -147,7 +145,8 @@ void do_project_filter(const wx_table *t, const char *expr, const char *cond, co
   if ((L.flags & WX_F_SYNC) || h_count) check_errors(op.w);
 }
 
-// n_exprs outputs of one filtered result in one pass (wx_select.hip); one
+// n_exprs outputs of one filtered result in one pass (wx_select.hip's hooks
+// over wx_compact_multi.hip's kernels); one
 // expression is the single-output call itself.  With no WHERE every row
 // passes through the same kernel.
 void do_project_filter_multi(const wx_table *t, const char *const *exprs, int32_t n_exprs, const char *cond,
@@ -163,9 +162,7 @@ void do_project_filter_multi(const wx_table *t, const char *const *exprs, int32_
   const wx_launch L = launch_of(Lp);
   if (mode < WX_MODE_DENSE || mode > WX_MODE_COMPACT) fail(WX_ERR_INVALID, "unknown mode");
   if (mode != WX_MODE_COMPACT) fail(WX_ERR_UNSUPPORTED, "more than one output needs WX_MODE_COMPACT");
-  if (d_out_idx && idx_bytes != 4 && idx_bytes != 8) fail(WX_ERR_INVALID, "idx_bytes must be 4 or 8");
-  if (d_out_idx && idx_bytes == 4 && row_base + t->n_rows > INT32_MAX)
-    fail(WX_ERR_INVALID, "row indices exceed int32; use idx_bytes = 8");
+  check_row_ids(t, d_out_idx, idx_bytes, row_base);
   const Spec spec = select_spec(t, exprs, n_exprs, cond, L);
   Op op(L, spec);
   // the status words and the ticket are the single-output kernel's

@@ -95,9 +95,7 @@ void do_window_select(const wx_table *t, const char *const *exprs, int32_t n_exp
   const wx_launch L = launch_of(Lp);
   if (L.flags & WX_F_ROW_ORDER)
     fail(WX_ERR_UNSUPPORTED, "row-order sums are not available for window aggregates");
-  if (d_out_idx && idx_bytes != 4 && idx_bytes != 8) fail(WX_ERR_INVALID, "idx_bytes must be 4 or 8");
-  if (d_out_idx && idx_bytes == 4 && row_base + t->n_rows > INT32_MAX)
-    fail(WX_ERR_INVALID, "row indices exceed int32; use idx_bytes = 8");
+  check_row_ids(t, d_out_idx, idx_bytes, row_base);
   if (group_capacity < 1) fail(WX_ERR_INVALID, "group_capacity must be at least 1");
   if (group_capacity > INT32_MAX) fail(WX_ERR_INVALID, "group_capacity exceeds the int32 key space");
   if ((int64_t)key_lo + WX_GROUP_WINDOW - 1 > INT32_MAX) fail(WX_ERR_INVALID, "key window out of range");

@@ -220,6 +220,7 @@ inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 
 void fill_cols(const wx_table *t, const std::vector<UsedCol> &cols, const void **dst);
 void check_table(const wx_table *t);
 void check_select_exprs(const char *const *exprs, int32_t n_exprs);
+void check_row_ids(const wx_table *t, const void *d_out_idx, int32_t idx_bytes, int64_t row_base);
 void check_gather_args(const wx_table *t, const char *const *exprs, int32_t n_exprs, int32_t idx_bytes, int64_t count);
 wx_launch default_launch();
 inline wx_launch launch_of(const wx_launch *Lp) { return Lp ? *Lp : default_launch(); }
