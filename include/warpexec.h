@@ -477,6 +477,22 @@ wx_status wx_topk(const wx_table *table, const char *order_expr, const char *con
                   const char *select_expr, int32_t k, int32_t descending,
                   const wx_launch *launch, int64_t row_base, float *d_keys, int64_t *d_idx,
                   float *d_vals, int64_t *d_count, int64_t *h_count, char *err, size_t errlen);
+/* The launch plan wx_topk follows for a table of n_rows rows and LIMIT k
+ * under the current diagnostic define list (WX_UNROLL, WX_TOPK_GRID,
+ * WX_TOPK_SEED, WX_TOPK_SEED_MINK of WARPDB_EXTRA_DEFINES): the same
+ * arithmetic as the run path's.  cus > 0: a device of that many compute
+ * units (needs no device); cus <= 0: the launch's device.  Workgroup b of the
+ * scan runs the spans b, b + grid, ... of span_rows rows each, one batch per
+ * span. */
+typedef struct wx_topk_geometry {
+  int64_t grid;             /* workgroups of the scan */
+  int64_t span_rows;        /* rows of one batch span */
+  int64_t max_batches;      /* the most batches any workgroup runs */
+  int64_t seed_grid;        /* workgroups of the seed pass, 0 = no seed pass */
+  int64_t seed_stride_rows; /* rows between the seed workgroups' spans */
+} wx_topk_geometry;
+wx_status wx_topk_plan(int64_t n_rows, int32_t k, int32_t cus, const wx_launch *launch, wx_topk_geometry *out,
+                       char *err, size_t errlen);
 
 /* One shard's ORDER BY .. LIMIT candidates in the exchange layout (520 bytes):
  * wx_topk's d_keys / d_vals / d_idx / d_count pointed at keys, vals, rows and

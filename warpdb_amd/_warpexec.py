@@ -95,6 +95,7 @@ EXPORTED_SYMBOLS = (
     "wx_head_merge",
     "wx_cast",
     "wx_topk",
+    "wx_topk_plan",
     "wx_sort_pairs",
     "wx_sort_float",
     "wx_sort_float_from",
@@ -129,6 +130,11 @@ class WxStats(ctypes.Structure):
 
 class WxWindowItem(ctypes.Structure):
     _fields_ = [("val_expr", ctypes.c_char_p), ("agg", ctypes.c_int32)]
+
+
+class WxTopkGeometry(ctypes.Structure):
+    _fields_ = [("grid", ctypes.c_int64), ("span_rows", ctypes.c_int64), ("max_batches", ctypes.c_int64),
+                ("seed_grid", ctypes.c_int64), ("seed_stride_rows", ctypes.c_int64)]
 
 
 class WxLaunch(ctypes.Structure):
@@ -196,6 +202,7 @@ def load() -> ctypes.CDLL:
         "wx_group_merge_lists": [P, I32, I64, P, I32, L, I64, P, P, P, P, pI64, E, S],
         "wx_cast": [P, I32, P, I32, I64, L, E, S],
         "wx_topk": [T, E, E, E, I32, I32, L, I64, P, P, P, P, pI64, E, S],
+        "wx_topk_plan": [I64, I32, I32, L, ctypes.POINTER(WxTopkGeometry), E, S],
         "wx_sort_pairs": [P, P, I64, I32, L, E, S],
         "wx_sort_float": [P, I64, I32, L, E, S],
         "wx_sort_float_from": [P, P, I64, I32, L, E, S],
@@ -672,6 +679,19 @@ def topk(table: Table, order_expr: str, cond: Optional[str], select_expr: Option
                      d_vals or None, d_count or None, ctypes.byref(h) if want_count else None, err, len(err))
     _check(st, err)
     return h.value if want_count else None
+
+
+def topk_plan(n_rows: int, k: int, cus: int = 0, launch: Optional[WxLaunch] = None) -> WxTopkGeometry:
+    """The launch plan wx_topk follows under the current WARPDB_EXTRA_DEFINES:
+    .grid, .span_rows, .max_batches (of the workgroup that runs the most),
+    .seed_grid (0: no seed pass), .seed_stride_rows.  cus > 0 names the
+    device's compute units (no device needed); otherwise the launch's device."""
+    lib = load()
+    err = _err()
+    out = WxTopkGeometry()
+    _check(lib.wx_topk_plan(n_rows, k, cus, ctypes.byref(launch) if launch is not None else None, ctypes.byref(out),
+                            err, len(err)), err)
+    return out
 
 
 def sort_pairs(d_keys: int, d_vals: int, count: int, ascending: bool, launch: WxLaunch) -> None:

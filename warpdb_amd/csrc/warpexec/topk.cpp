@@ -4,6 +4,44 @@
 
 namespace wx {
 
+// The launch plan of a top-K query: the one statement of the scan's and the
+// seed pass's geometry (do_topk launches it, wx_topk_plan reports it).
+//
+// Scan: workgroup b runs the spans b, b + grid, ... of `span` quads each.
+// The grid is one workgroup per WX_BLOCK quads up to two per CU
+// (profiles/r01/ablate_topk_grid_bound.txt: few waves publish early bounds);
+// WX_TOPK_GRID (diagnostic define) caps it further and changes nothing else,
+// so that a small table runs many batches per workgroup.
+//
+// Seed pass (wx_topk_seed): one span per workgroup at evenly spaced
+// offsets, ~1M rows, its exact K-th best raised into slot 0 before the
+// scan.  WX_TOPK_SEED (diagnostic define) 0 = off, 1 = K >= 5 over tables
+// of >= 2^24 rows (the default; WX_TOPK_SEED_MINK moves the K bound), 2 =
+// any table of two spans or more.  Per 1e9 rows: K = 5 (C5) scan 0.607-0.612
+// -> 0.564 ms, query 0.649-0.656 -> 0.644-0.649; K = 8 query -17..-22 us;
+// K = 2 neutral (profiles/r06/topk_seed_k_le8.txt); K = 9 / 16 / 32 0.79 /
+// 0.89 / 1.31 ms instead of 0.85 / 1.04 / 1.94 (profiles/r05/topk_seed.txt).
+TopkPlan topk_plan(int64_t n_rows, int32_t k, int cus, const std::string &extra) {
+  TopkPlan P;
+  P.nq = (n_rows + 3) / 4;
+  P.grid = grid_for(P.nq, cus, 2);
+  const int cap = define_value(extra, "WX_TOPK_GRID", 0);
+  if (cap >= 1 && P.grid > (unsigned)cap) P.grid = (unsigned)cap;
+  P.span = (int64_t)WX_BLOCK * define_value(extra, "WX_UNROLL", 8);  // quads per batch
+  if (P.span < 1) fail(WX_ERR_INVALID, "WX_UNROLL must be at least 1");
+  const int seed_mode = define_value(extra, "WX_TOPK_SEED", 1);
+  const int seed_min_k = define_value(extra, "WX_TOPK_SEED_MINK", 5);
+  const int64_t spans = P.nq / P.span;
+  const bool seed =
+      spans >= 2 && (seed_mode == 2 || (seed_mode == 1 && k >= seed_min_k && n_rows >= ((int64_t)1 << 24)));
+  P.seed_grid = seed ? std::min<int64_t>(spans, WX_TOPK_SEED_SPANS) : 0;
+  P.seed_stride = seed ? (spans / P.seed_grid) * P.span : 0;
+  // workgroup 0 runs the most batches: every grid-th of the span positions
+  const int64_t positions = (P.nq + P.span - 1) / P.span;
+  P.max_batches = (positions + P.grid - 1) / P.grid;
+  return P;
+}
+
 void do_topk(const wx_table *t, const char *order_expr, const char *cond, const char *select_expr, int32_t k,
              int32_t desc, const wx_launch *Lp, int64_t row_base, float *d_keys, int64_t *d_idx, float *d_vals,
              int64_t *d_count, int64_t *h_count) {
@@ -13,23 +51,10 @@ void do_topk(const wx_table *t, const char *order_expr, const char *cond, const 
   if (k < 1 || k > WX_TOPK_MAX) fail(WX_ERR_UNSUPPORTED, "LIMIT must be between 1 and 32");
   const Spec spec = topk_spec(t, order_expr, cond, select_expr, k, desc, L);
   Op op(L, spec);
-  const unsigned grid = grid_for((t->n_rows + 3) / 4, op.d.cus, 2);  // profiles/r01/ablate_topk_grid_bound.txt: few waves publish early bounds
-  const int64_t span = (int64_t)WX_BLOCK * define_value(spec.extra, "WX_UNROLL", 8);  // quads per batch
-  const int64_t nq = (t->n_rows + 3) / 4;
-  // Seed pass (wx_topk_seed): one span per workgroup at evenly spaced
-  // offsets, ~1M rows, its exact K-th best raised into slot 0 before the
-  // scan.  WX_TOPK_SEED (diagnostic define) 0 = off, 1 = K >= 5 over tables
-  // of >= 2^24 rows (the default; WX_TOPK_SEED_MINK moves the K bound), 2 =
-  // any table of two spans or more.  Per 1e9 rows: K = 5 (C5) scan 0.607-0.612
-  // -> 0.564 ms, query 0.649-0.656 -> 0.644-0.649; K = 8 query -17..-22 us;
-  // K = 2 neutral (profiles/r06/topk_seed_k_le8.txt); K = 9 / 16 / 32 0.79 /
-  // 0.89 / 1.31 ms instead of 0.85 / 1.04 / 1.94 (profiles/r05/topk_seed.txt).
-  const int seed_mode = define_value(spec.extra, "WX_TOPK_SEED", 1);
-  const int seed_min_k = define_value(spec.extra, "WX_TOPK_SEED_MINK", 5);
-  const int64_t spans = nq / span;
-  const bool seed =
-      spans >= 2 && (seed_mode == 2 || (seed_mode == 1 && k >= seed_min_k && t->n_rows >= ((int64_t)1 << 24)));
-  const int64_t gs = seed ? std::min<int64_t>(spans, WX_TOPK_SEED_SPANS) : 0;
+  const TopkPlan P = topk_plan(t->n_rows, k, op.d.cus, spec.extra);
+  const unsigned grid = P.grid;
+  const int64_t span = P.span, nq = P.nq, gs = P.seed_grid;
+  const bool seed = gs > 0;
   // candidates of the scan's grid, or of the seed's workgroups when a device
   // with few CUs gives the scan the smaller grid
   const size_t n_cand_max = (size_t)std::max<int64_t>(grid, gs) * k;
@@ -53,7 +78,7 @@ void do_topk(const wx_table *t, const char *order_expr, const char *cond, const 
   a.n_rows = t->n_rows;
   if (seed) {
     WxTopkArgs sa = a;
-    sa.q_stride = (spans / gs) * span;
+    sa.q_stride = P.seed_stride;
     sa.q_step = nq;  // one batch per workgroup
     launch(op.mod->fn("wx_topk_seed"), (unsigned)gs, &sa, op.s, false);
     WxTopkFinArgs sf;

@@ -278,6 +278,22 @@ wx_status wx_topk(const wx_table *table, const char *order_expr, const char *con
   });
 }
 
+wx_status wx_topk_plan(int64_t n_rows, int32_t k, int32_t cus, const wx_launch *launch_, wx_topk_geometry *out,
+                       char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    if (!out) fail(WX_ERR_INVALID, "null plan output");
+    if (n_rows < 0) fail(WX_ERR_INVALID, "negative row count");
+    if (k < 1 || k > WX_TOPK_MAX) fail(WX_ERR_UNSUPPORTED, "LIMIT must be between 1 and 32");
+    if (cus <= 0) cus = device_state(launch_of(launch_).device, true).cus;
+    const TopkPlan P = topk_plan(n_rows, k, cus, env_or("WARPDB_EXTRA_DEFINES", ""));
+    out->grid = P.grid;
+    out->span_rows = P.span * 4;
+    out->max_batches = P.max_batches;
+    out->seed_grid = P.seed_grid;
+    out->seed_stride_rows = P.seed_stride * 4;
+  });
+}
+
 wx_status wx_sort_pairs(int32_t *d_keys, float *d_vals, int64_t count, int32_t ascending, const wx_launch *launch_,
                         char *err, size_t errlen) {
   return guarded(err, errlen, [&] { do_sort(d_keys, d_vals, count, 1, ascending, launch_); });

@@ -395,6 +395,15 @@ void do_sort(void *d_a, float *d_v, int64_t count, int kind, int32_t ascending, 
              int64_t limit = -1, const void *src = nullptr);
 
 // topk.cpp
+struct TopkPlan {
+  unsigned grid = 1;        // scan workgroups
+  int64_t nq = 0;           // row quads of the table
+  int64_t span = 0;         // quads per batch span
+  int64_t max_batches = 0;  // batches of the workgroup that runs the most
+  int64_t seed_grid = 0;    // seed workgroups (0: no seed pass)
+  int64_t seed_stride = 0;  // quads between the seed workgroups' spans
+};
+TopkPlan topk_plan(int64_t n_rows, int32_t k, int cus, const std::string &extra);
 void do_topk(const wx_table *t, const char *order_expr, const char *cond, const char *select_expr, int32_t k,
              int32_t desc, const wx_launch *Lp, int64_t row_base, float *d_keys, int64_t *d_idx, float *d_vals,
              int64_t *d_count, int64_t *h_count);
