@@ -136,6 +136,12 @@ struct QueryAST {
   bool distinct = false;
 };
 
+// JOIN may be written [INNER] JOIN or LEFT [OUTER] JOIN (an extension: the
+// reference parses a bare JOIN only).  JoinClause and QueryAST keep the size
+// and layout of this header's earlier versions: programs built against those
+// and not rebuilt (the prebuilt reference tests among them) inline the
+// structs' destructors and run against a newer libwarpdb.so.  So the kind of
+// a JOIN is not a member; the planner reads it off the tokens (plan.hpp).
 QueryAST parse_query(const std::vector<Token> &tokens);
 
 namespace warpdb {

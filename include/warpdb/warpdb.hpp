@@ -22,6 +22,10 @@ struct ResultTable {
   std::vector<std::string> names;
   std::vector<std::vector<float>> columns;
   std::vector<int64_t> rows;
+  // joined results (query_join, query_sql_joined): the matched row of the
+  // attached table for each result row, -1 for an unmatched row of a LEFT
+  // join; empty everywhere else
+  std::vector<int64_t> right_rows;
 };
 // Result column names of a SELECT list, without running anything: a bare
 // column keeps its name, an aggregate is agg_kernel() + "_" + its position
@@ -152,6 +156,31 @@ class WarpDB {
                                   const std::string &order_by, bool descending, int64_t limit, int64_t offset,
                                   ArrowArray *out_array, ArrowSchema *out_schema);
 
+  // Joins.  attach loads a second table (.csv with an optional schema, or
+  // .json) into HBM of the same device under `name`; attaching again under
+  // the same name replaces it.  query_join / query_sql_joined run a PK-FK
+  // equi-join of this table (the left, fact side) with an attached one (the
+  // right, dimension side): every left row matches at most one right row,
+  // the right key is an INT32 column whose values are unique, and the result
+  // is one row per left row the join keeps, in left row order, with the left
+  // row ids in `rows` and the matched right rows in `right_rows`.
+  enum class JoinType { Inner, Left };
+  void attach(const std::string &name, const std::string &filepath, const std::vector<DataType> &schema = {});
+  // exprs and where are expressions over the columns of both tables (a name
+  // in both must be qualified: t.x with this table's FROM name `left_name`,
+  // or <name>.x); left_key is an expression over this table's columns,
+  // right_key a column of the attached table.  INNER keeps the rows WHERE
+  // keeps and that match; LEFT keeps the rows WHERE keeps, an expression
+  // that names a right column being NaN for an unmatched row.
+  ResultTable query_join(const std::string &name, const std::string &left_key, const std::string &right_key,
+                         const std::vector<std::string> &exprs, const std::string &where = "",
+                         JoinType join_type = JoinType::Inner);
+  // SELECT items FROM t [INNER] JOIN u ON <expression over t> = <column of u>
+  // [WHERE c] [LIMIT n] [OFFSET m], or LEFT [OUTER] JOIN; u is an attached
+  // table.  GROUP BY, HAVING, DISTINCT, ORDER BY, aggregates, window items
+  // and a second JOIN are refused.
+  ResultTable query_sql_joined(const std::string &sql);
+
   const Table &table() const { return table_; }
   const HostTable &host_table() const { return host_table_; }
 
@@ -159,6 +188,13 @@ class WarpDB {
   warpdb::ResidentShards &shards();
   Table table_;
   HostTable host_table_;
+  // attach()'s tables live beside the object, keyed by it (warpdb.cpp), not
+  // in a member: programs built against this header's earlier versions and not
+  // rebuilt (the prebuilt reference tests among them) allocate a WarpDB of
+  // the size it had, and the constructor must not write past it.  A query
+  // holds its table by a shared pointer, so attach() may replace a table
+  // while another thread's join still reads the old one.
+  std::shared_ptr<const Table> attached(const std::string &name) const;  // null: none under that name
   std::unique_ptr<warpdb::ResidentShards> shards_;  // query_multi_gpu*: built on first use
   std::once_flag shards_once_;                      // the bindings release the GIL: one builder
 };

@@ -469,6 +469,68 @@ wx_status wx_prepare_window(const wx_table *table, const char *const *exprs, int
  * WX_COMPACT_DWAVES of WARPDB_EXTRA_DEFINES like wx_select_tile_rows. */
 int32_t wx_window_tile_rows(int32_t n_outputs, int32_t n_items, int32_t search);
 
+/* PK-FK equi-join: the rows of `left` that cond keeps, each looked up in
+ * `right` by (int)left_key_expr == right_key_col, in ascending left row order
+ * -- wx_project_filter_multi's result over the columns of both tables.  Every
+ * left row matches at most one right row: right_key_col is a bare INT32
+ * column of `right` whose values are unique (a key that occurs twice returns
+ * WX_ERR_UNSUPPORTED, "JOIN: the right key is not unique (key <k>)").
+ * exprs (1 .. WX_ORDERED_MAX_EXPRS) and cond are lowered C text over the
+ * columns of both tables and may mix them; an identifier that names a column
+ * in both tables returns WX_ERR_INVALID ("column <x> is in both tables");
+ * left_key_expr may name left columns only.  At most 16 columns of each table
+ * may be referenced; `right` holds at most 2^26 rows; WX_F_ROW_ORDER returns
+ * WX_ERR_UNSUPPORTED.
+ * WX_JOIN_INNER keeps the rows that cond keeps and that match.  WX_JOIN_LEFT
+ * keeps the rows that cond keeps (a cond that names a right column is false
+ * for an unmatched row); an output that names a right column is NaN for an
+ * unmatched row.  With no right rows an INNER join is empty and a LEFT join
+ * is the filtered left table.
+ * d_out_vals holds n_exprs device pointers, each nullable; d_out_right_row
+ * (device int32, nullable, n_rows entries) receives the matched right row of
+ * every kept row, -1 for an unmatched one; row ids, d_count / h_count,
+ * idx_bytes and row_base behave as in wx_project_filter_multi, and nothing is
+ * written at positions >= count.
+ * Run: one reduction finds the smallest and the largest right key and the
+ * call synchronises the stream once to read them: a span of at most 4096 keys
+ * takes the direct form (rows[key - min], copied into LDS per workgroup), a
+ * wider one the hash form (open addressing, linear probing, the smallest
+ * power of two >= 2 * n_right and >= 64 slots of {key, row}).  The table is
+ * built, a second synchronisation reads the duplicate report, then one
+ * probing compaction runs per chunk of WX_MAX_OUTPUTS outputs: the first
+ * writes the row ids, the right rows and the count, later ones repeat the
+ * probe for their outputs.  With WX_F_TIME only the probing compactions are
+ * timed.  $WARPDB_JOIN_FORM=hash forces the hash form (a test hook). */
+#define WX_JOIN_INNER 0
+#define WX_JOIN_LEFT 1
+wx_status wx_join_select(const wx_table *left, const wx_table *right, const char *left_key_expr,
+                         const char *right_key_col, int32_t join_type, const char *const *exprs, int32_t n_exprs,
+                         const char *cond, const wx_launch *launch, float *const *d_out_vals, void *d_out_idx,
+                         int32_t idx_bytes, int64_t row_base, int32_t *d_out_right_row, int64_t *d_count,
+                         int64_t *h_count, char *err, size_t errlen);
+/* Build (and cache) the modules wx_join_select would use -- the build module
+ * and every probe launch, in the direct (form == 0) or the hash (form == 1)
+ * form, with or without the right-row output -- without launching (works
+ * without a GPU, like wx_prepare). */
+wx_status wx_prepare_join(const wx_table *left, const wx_table *right, const char *left_key_expr,
+                          const char *right_key_col, int32_t join_type, const char *const *exprs, int32_t n_exprs,
+                          const char *cond, const wx_launch *launch, int32_t with_right_row, int32_t form, char *err,
+                          size_t errlen);
+/* Rows per tile of one probe launch of n_outputs outputs (1 ..
+ * WX_MAX_OUTPUTS) in the direct (0) or the hash (1) form, with or without
+ * the right-row output; 0 when an argument is out of range.  Follows
+ * WX_COMPACT_GROUPS / WX_COMPACT_DWAVES of WARPDB_EXTRA_DEFINES. */
+int32_t wx_join_tile_rows(int32_t n_outputs, int32_t form, int32_t with_right_row);
+/* The form wx_join_select takes for a right table of n_right rows whose keys
+ * lie in [key_min, key_max] (*form: 0 direct, 1 hash) and the hash table's
+ * log2 capacity (0 in the direct form); n_right above 2^26 returns
+ * WX_ERR_UNSUPPORTED.  Needs no device. */
+wx_status wx_join_plan(int64_t n_right, int32_t key_min, int32_t key_max, int32_t *form, int32_t *log2_capacity,
+                       char *err, size_t errlen);
+/* The home slot of a key in a hash table of 1 << log2_capacity slots, as the
+ * kernels compute it; -1 when log2_capacity is outside 6 .. 27. */
+int32_t wx_join_hash_slot(int32_t key, int32_t log2_capacity);
+
 /* ORDER BY order_expr [DESC] LIMIT k (1 <= k <= 32) over rows where cond
  * holds; ties broken by ascending row index.  Outputs (device, nullable):
  * order keys, row_base + row indices, and (float)select_expr at those rows

@@ -64,6 +64,10 @@ MODE_COMPACT = 2
 MAX_OUTPUTS = 4
 GROUP_MAX_VALUES = 4  # WX_GROUP_MAX_VALUES  # WX_MAX_OUTPUTS: expressions of one project_filter_multi call
 WIN_SUM, WIN_AVG, WIN_COUNT, WIN_MIN, WIN_MAX = 0, 1, 2, 3, 4  # wx_window_item.agg
+JOIN_INNER, JOIN_LEFT = 0, 1  # wx_join_select's join_type
+JOIN_DIRECT, JOIN_HASH = 0, 1  # the form of a join's table (wx_join_plan)
+JOIN_DIRECT_BINS = 4096  # widest key span of the direct form
+JOIN_MAX_RIGHT = 1 << 26  # most rows of a right table
 
 OP_DENSE, OP_COMPACT, OP_SUM, OP_GROUP, OP_TOPK, OP_UTIL = 0, 1, 2, 3, 4, 5
 
@@ -85,6 +89,11 @@ EXPORTED_SYMBOLS = (
     "wx_window_select",
     "wx_prepare_window",
     "wx_window_tile_rows",
+    "wx_join_select",
+    "wx_prepare_join",
+    "wx_join_tile_rows",
+    "wx_join_plan",
+    "wx_join_hash_slot",
     "wx_group_partials",
     "wx_group_combine",
     "wx_group_partials_slots",
@@ -192,6 +201,10 @@ def load() -> ctypes.CDLL:
         "wx_window_select": [T, ctypes.POINTER(E), I32, ctypes.POINTER(WxWindowItem), I32, E, E, L, I32, I64,
                              ctypes.POINTER(P), P, I32, I64, P, pI64, E, S],
         "wx_prepare_window": [T, ctypes.POINTER(E), I32, ctypes.POINTER(WxWindowItem), I32, E, E, L, I32, E, S],
+        "wx_join_select": [T, T, E, E, I32, ctypes.POINTER(E), I32, E, L, ctypes.POINTER(P), P, I32, I64, P, P, pI64, E,
+                           S],
+        "wx_prepare_join": [T, T, E, E, I32, ctypes.POINTER(E), I32, E, L, I32, I32, E, S],
+        "wx_join_plan": [I64, I32, I32, ctypes.POINTER(I32), ctypes.POINTER(I32), E, S],
         "wx_group_partials": [T, E, E, E, L, I32, P, I64, P, P, P, P, pI64, E, S],
         "wx_group_combine": [P, I32, P, P, P, I64, L, I64, P, P, P, P, pI64, E, S],
         "wx_group_partials_slots": [T, E, E, E, L, I32, P, I32, I32, I32, I64, P, P, P, P, pI64, E, S],
@@ -227,6 +240,10 @@ def load() -> ctypes.CDLL:
     lib.wx_select_tile_rows.restype = ctypes.c_int32
     lib.wx_window_tile_rows.argtypes = [I32, I32, I32]
     lib.wx_window_tile_rows.restype = ctypes.c_int32
+    lib.wx_join_tile_rows.argtypes = [I32, I32, I32]
+    lib.wx_join_tile_rows.restype = ctypes.c_int32
+    lib.wx_join_hash_slot.argtypes = [I32, I32]
+    lib.wx_join_hash_slot.restype = ctypes.c_int32
     lib.wx_gather_tile_rows.argtypes = [I32]
     lib.wx_gather_tile_rows.restype = ctypes.c_int32
     lib.wx_sort_tile_keys.argtypes = [I32]
@@ -540,6 +557,60 @@ def prepare_window(table: Table, exprs: Sequence[str], items: Sequence[Tuple[Opt
 def window_tile_rows(n_outputs: int, n_items: int, search: bool = False) -> int:
     """Rows per tile of one broadcast launch (0: out of range)."""
     return int(load().wx_window_tile_rows(n_outputs, n_items, int(search)))
+
+
+def join_select(left: Table, right: Table, left_key_expr: str, right_key_col: str, exprs: Sequence[str],
+                cond: Optional[str], launch: WxLaunch, d_out_vals: Sequence[int], join_type: int = JOIN_INNER,
+                d_out_idx: int = 0, idx_bytes: int = 8, row_base: int = 0, d_out_right_row: int = 0,
+                d_count: int = 0, want_count: bool = False) -> Optional[int]:
+    """PK-FK equi-join: the rows of `left` that cond keeps, each looked up in
+    `right` by (int)left_key_expr == right_key_col, in left row order.
+    d_out_vals[j] (0 = not wanted) receives expression j (over the columns of
+    both tables), d_out_idx the left row ids, d_out_right_row (int32) the
+    matched right rows (-1: none, a LEFT join).  A shorter d_out_vals is
+    padded with nulls."""
+    lib = load()
+    err = _err()
+    h = ctypes.c_int64(-1)
+    outs = list(d_out_vals) + [0] * (len(exprs) - len(d_out_vals))
+    ptrs = (ctypes.c_void_p * max(1, len(outs)))(*[p or None for p in outs])
+    st = lib.wx_join_select(ctypes.byref(left.c), ctypes.byref(right.c), _enc(left_key_expr), _enc(right_key_col),
+                            join_type, _expr_array(exprs), len(exprs), _enc(cond), ctypes.byref(launch), ptrs,
+                            d_out_idx or None, idx_bytes, row_base, d_out_right_row or None, d_count or None,
+                            ctypes.byref(h) if want_count else None, err, len(err))
+    _check(st, err)
+    return h.value if want_count else None
+
+
+def prepare_join(left: Table, right: Table, left_key_expr: str, right_key_col: str, exprs: Sequence[str],
+                 cond: Optional[str] = None, launch: Optional[WxLaunch] = None, join_type: int = JOIN_INNER,
+                 with_right_row: bool = False, form: int = JOIN_HASH) -> None:
+    """Compile the modules join_select would use, in the direct or the hash form (no GPU needed)."""
+    lib = load()
+    err = _err()
+    L = launch or make_launch()
+    _check(lib.wx_prepare_join(ctypes.byref(left.c), ctypes.byref(right.c), _enc(left_key_expr), _enc(right_key_col),
+                               join_type, _expr_array(exprs), len(exprs), _enc(cond), ctypes.byref(L),
+                               1 if with_right_row else 0, form, err, len(err)), err)
+
+
+def join_tile_rows(n_outputs: int, form: int = JOIN_HASH, with_right_row: bool = False) -> int:
+    """Rows per tile of one probe launch (0: out of range)."""
+    return int(load().wx_join_tile_rows(n_outputs, form, int(with_right_row)))
+
+
+def join_plan(n_right: int, key_min: int, key_max: int) -> Tuple[int, int]:
+    """(form, log2 capacity) of the table join_select builds for n_right keys in [key_min, key_max]."""
+    lib = load()
+    err = _err()
+    form, log2cap = ctypes.c_int32(-1), ctypes.c_int32(-1)
+    _check(lib.wx_join_plan(n_right, key_min, key_max, ctypes.byref(form), ctypes.byref(log2cap), err, len(err)), err)
+    return form.value, log2cap.value
+
+
+def join_hash_slot(key: int, log2_capacity: int) -> int:
+    """The home slot the kernels use for `key` in a table of 1 << log2_capacity slots."""
+    return int(load().wx_join_hash_slot(key, log2_capacity))
 
 
 def group_partials(table: Table, val_expr: str, key_expr: str, cond: Optional[str], launch: WxLaunch,

@@ -6,16 +6,24 @@
 //   WX_CM_NOUT                outputs of the launch, 1 .. WX_SELECT_MAX_OUT
 //   WX_CM_ARGS                the argument block: a struct whose member c is
 //                             the WxCompactArgs and out_val the output arrays
-//   WX_CM_MASK                bit j set: output j is WX_WIN_GET(j), else
+//   WX_CM_MASK                bit j set: output j is WX_CM_GET(j), else
 //                             static_cast<float>(WX_EXPR / WX_EXPR1 .. WX_EXPR3)
-//   WX_CM_ROW()               what a row works out before its outputs
+//   WX_CM_ROW()               what a row works out before its WHERE and its
+//                             outputs (declarations in the row's scope)
+//   WX_CM_KEEP()              optional: a predicate of what WX_CM_ROW() found
+//                             that a passing row must meet too (default true)
+//   WX_CM_NSTAGE, WX_CM_XEVAL()  optional: WX_CM_NOUT + 1 and the statement
+//                             that sets wx_val[WX_CM_NOUT][wx_g][wx_e], one
+//                             more staged 4-byte value, written to
+//                             out_val[WX_CM_NOUT] (default: none)
 //   WX_CM_SETUP()             what a kernel works out once
 //   WX_CM_LDS                 the family's own __shared__ declarations
 //   WX_CM_FILL_LDS(NTHREADS)  fills them, by all NTHREADS threads of the
 //                             workgroup, before the kernel's first barrier
 //   WX_CM_DEEP, WX_CM_TICKET  the names of the two kernels
 // wx_select.hip is the plain case (mask 0, every other hook empty);
-// wx_window.hip looks a row's partition up in WX_CM_ROW().
+// wx_window.hip looks a row's partition up in WX_CM_ROW(); wx_join.hip probes
+// the right table there and keeps a row by what the probe found.
 
 // ===========================================================================
 #if WX_OP == WX_OP_COMPACT && defined(WX_CM_NOUT)
@@ -32,49 +40,56 @@
 #if WX_CM_NOUT < 1 || WX_CM_NOUT > WX_SELECT_MAX_OUT
 #error "WX_CM_NOUT must be between 1 and 4"
 #endif
+#ifndef WX_CM_KEEP
+#define WX_CM_KEEP() true
+#endif
+#ifndef WX_CM_NSTAGE
+#define WX_CM_NSTAGE WX_CM_NOUT
+#define WX_CM_XEVAL()
+#endif
 #if WX_COMPACT_GROUPS > 8
 #error "at most 8 row quads per thread: a thread's keep bits share one 32-bit word"
 #endif
 #if WX_CM_MASK & 1
-#define WX_CM_OUT0 wx_val[0][wx_g][wx_e] = WX_WIN_GET(0);
+#define WX_CM_OUT0 wx_val[0][wx_g][wx_e] = WX_CM_GET(0);
 #else
 #define WX_CM_OUT0 wx_val[0][wx_g][wx_e] = static_cast<float>(WX_EXPR);
 #endif
 #if WX_CM_NOUT < 2
 #define WX_CM_OUT1
 #elif WX_CM_MASK & 2
-#define WX_CM_OUT1 wx_val[1][wx_g][wx_e] = WX_WIN_GET(1);
+#define WX_CM_OUT1 wx_val[1][wx_g][wx_e] = WX_CM_GET(1);
 #else
 #define WX_CM_OUT1 wx_val[1][wx_g][wx_e] = static_cast<float>(WX_EXPR1);
 #endif
 #if WX_CM_NOUT < 3
 #define WX_CM_OUT2
 #elif WX_CM_MASK & 4
-#define WX_CM_OUT2 wx_val[2][wx_g][wx_e] = WX_WIN_GET(2);
+#define WX_CM_OUT2 wx_val[2][wx_g][wx_e] = WX_CM_GET(2);
 #else
 #define WX_CM_OUT2 wx_val[2][wx_g][wx_e] = static_cast<float>(WX_EXPR2);
 #endif
 #if WX_CM_NOUT < 4
 #define WX_CM_OUT3
 #elif WX_CM_MASK & 8
-#define WX_CM_OUT3 wx_val[3][wx_g][wx_e] = WX_WIN_GET(3);
+#define WX_CM_OUT3 wx_val[3][wx_g][wx_e] = WX_CM_GET(3);
 #else
 #define WX_CM_OUT3 wx_val[3][wx_g][wx_e] = static_cast<float>(WX_EXPR3);
 #endif
 // row (wx_g, wx_e) of the tile into wx_val
 #define WX_CM_EVAL() \
-  { WX_CM_ROW() WX_CM_OUT0 WX_CM_OUT1 WX_CM_OUT2 WX_CM_OUT3 }
+  { WX_CM_OUT0 WX_CM_OUT1 WX_CM_OUT2 WX_CM_OUT3 WX_CM_XEVAL() }
 
 // The pipelined kernel: wx_project_compact_deep's schedule (iteration k
 // evaluates and ranks t_k and issues t_{k+1}'s loads; the control wave
 // publishes t_k, takes the ticket of iteration k + 2 and resolves t_{k-1}
 // while the data waves write t_{k-2} out of LDS and stage t_k), with
-// 2 x WX_TILE x (4 * WX_CM_NOUT + 2) B of stage buffers beside WX_CM_LDS.
+// 2 x WX_TILE x (4 * WX_CM_NSTAGE + 2) B of stage buffers beside WX_CM_LDS.
 extern "C" __global__ __launch_bounds__(WX_CBLOCK, 1) void WX_CM_DEEP(WX_CM_ARGS wx_s) {
   const WxCompactArgs &wx_a = wx_s.c;
   const wx_u64 wx_E = (wx_u64)wx_a.epoch << WX_EPOCH_SHIFT;
   __shared__ wx_u32 s_cnt[WX_DWAVES][WX_GROUPS];
-  __shared__ float s_val[2][WX_CM_NOUT][WX_TILE];
+  __shared__ float s_val[2][WX_CM_NSTAGE][WX_TILE];
   __shared__ unsigned short s_off[2][WX_TILE];
   __shared__ wx_i64 s_excl[2];
   __shared__ wx_i64 s_tiles[4];
@@ -108,7 +123,7 @@ extern "C" __global__ __launch_bounds__(WX_CBLOCK, 1) void WX_CM_DEEP(WX_CM_ARGS
     const wx_i64 tile_base = tile * WX_TILE;
     const int cur = k & 1;  // t_k is staged in buffer cur, t_{k-2} is read from it first
     wx_u32 wx_kb = 0;
-    float wx_val[WX_CM_NOUT][WX_GROUPS][4];
+    float wx_val[WX_CM_NSTAGE][WX_GROUPS][4];
     wx_u32 lane_pre[WX_GROUPS];
     // phase 1 (data): evaluate t_k, issue t_{k+1}'s loads, rank t_k
     if (!control && have) {
@@ -121,8 +136,10 @@ extern "C" __global__ __launch_bounds__(WX_CBLOCK, 1) void WX_CM_DEEP(WX_CM_ARGS
           const wx_u32 wx_lrow = (wx_u32)(wx_g * (WX_DTHREADS * 4) + wx_dt * 4 + wx_e);
           const wx_i64 idx = tile_base + wx_lrow;
           (void)idx;
+          WX_CM_ROW()
           bool wx_k = wx_lrow < wx_rows;
           wx_k = wx_k && WX_EVAL_COND();
+          wx_k = wx_k && WX_CM_KEEP();
           wx_kb |= (wx_k ? 1u : 0u) << (wx_g * 4 + wx_e);
           WX_CM_EVAL()
         }
@@ -175,7 +192,7 @@ extern "C" __global__ __launch_bounds__(WX_CBLOCK, 1) void WX_CM_DEEP(WX_CM_ARGS
         const wx_i64 pos = j < n_head ? excl + j : b1 + (j - n_head);
         const int i = (int)(pos - excl);
 #pragma unroll
-        for (int o = 0; o < WX_CM_NOUT; ++o)
+        for (int o = 0; o < WX_CM_NSTAGE; ++o)
           if (wx_s.out_val[o]) wx_s.out_val[o][pos] = s_val[cur][o][i];
         if (wx_a.out_idx) {
           const wx_i64 gi = prev_base + so[i];
@@ -186,7 +203,7 @@ extern "C" __global__ __launch_bounds__(WX_CBLOCK, 1) void WX_CM_DEEP(WX_CM_ARGS
       for (wx_i64 q = b0 + 4 * (wx_i64)wx_dt; q < b1; q += 4 * (wx_i64)WX_DTHREADS) {
         const int i = (int)(q - excl);
 #pragma unroll
-        for (int o = 0; o < WX_CM_NOUT; ++o) {
+        for (int o = 0; o < WX_CM_NSTAGE; ++o) {
           if (wx_s.out_val[o]) {
             typedef float v4f __attribute__((ext_vector_type(4)));
             const float *sv = s_val[cur][o];
@@ -235,7 +252,7 @@ extern "C" __global__ __launch_bounds__(WX_CBLOCK, 1) void WX_CM_DEEP(WX_CM_ARGS
         for (int e = 0; e < 4; ++e) {
           if ((wx_kb >> (g * 4 + e)) & 1u) {
 #pragma unroll
-            for (int o = 0; o < WX_CM_NOUT; ++o) s_val[cur][o][pos] = wx_val[o][g][e];
+            for (int o = 0; o < WX_CM_NSTAGE; ++o) s_val[cur][o][pos] = wx_val[o][g][e];
             s_off[cur][pos] = (unsigned short)(g * (WX_DTHREADS * 4) + wx_dt * 4 + e);
             ++pos;
           }
@@ -277,7 +294,7 @@ extern "C" __global__ __launch_bounds__(WX_DTHREADS) void WX_CM_TICKET(WX_CM_ARG
     for (int wx_g = 0; wx_g < WX_GROUPS; ++wx_g) { WX_COLS(WX_LOAD_TILE_IN) }
   }
   bool wx_keep[WX_GROUPS][4];
-  float wx_val[WX_CM_NOUT][WX_GROUPS][4];
+  float wx_val[WX_CM_NSTAGE][WX_GROUPS][4];
   wx_u32 lane_pre[WX_GROUPS];
 #pragma unroll
   for (int wx_g = 0; wx_g < WX_GROUPS; ++wx_g) {
@@ -285,8 +302,10 @@ extern "C" __global__ __launch_bounds__(WX_DTHREADS) void WX_CM_TICKET(WX_CM_ARG
     for (int wx_e = 0; wx_e < 4; ++wx_e) {
       WX_COLS(WX_BIND_TILE_IN)
       const wx_i64 idx = tile_base + (wx_i64)wx_g * (WX_DTHREADS * 4) + (wx_i64)wx_dt * 4 + wx_e;
+      WX_CM_ROW()
       bool wx_k = idx < wx_a.n_rows;
       wx_k = wx_k && WX_EVAL_COND();
+      wx_k = wx_k && WX_CM_KEEP();
       wx_keep[wx_g][wx_e] = wx_k;
       WX_CM_EVAL()
     }
@@ -328,7 +347,7 @@ extern "C" __global__ __launch_bounds__(WX_DTHREADS) void WX_CM_TICKET(WX_CM_ARG
     for (int e = 0; e < 4; ++e) {
       if (wx_keep[g][e]) {
 #pragma unroll
-        for (int o = 0; o < WX_CM_NOUT; ++o)
+        for (int o = 0; o < WX_CM_NSTAGE; ++o)
           if (wx_s.out_val[o]) wx_s.out_val[o][pos] = wx_val[o][g][e];
         if (wx_a.out_idx) {
           const wx_i64 gi = wx_a.row_base + r0 + e;

@@ -156,6 +156,7 @@ static_assert(((unsigned)WX_WIN_MASK >> WX_WIN_NOUT) == 0u && WX_WIN_NITEMS >= 1
 #define WX_CM_NOUT WX_WIN_NOUT
 #define WX_CM_ARGS WxWindowArgs
 #define WX_CM_MASK WX_WIN_MASK
+#define WX_CM_GET(j) WX_WIN_GET(j)
 #define WX_CM_ROW()                            \
   const int wx_key = static_cast<int>(WX_KEY); \
   WX_WIN_SLOT()

@@ -429,14 +429,30 @@ QueryAST parse_query(const std::vector<Token> &tokens) {
   if (pos >= end || tokens[pos].type != TokenType::Identifier)
     throw std::runtime_error("Expected table name after FROM" + where_at(at(pos)));
   q.from_table = tokens[pos++].value;
-  while (is_kw(pos, "JOIN")) {
+  // JOIN u ON c, with the optional words INNER, or LEFT [OUTER], in front
+  // (plain identifiers to the lexer: they count only right before JOIN)
+  auto is_word = [&](size_t p, const char *w) {
+    if (p >= end || tokens[p].type != TokenType::Identifier) return false;
+    std::string u = tokens[p].value;
+    for (char &ch : u) ch = static_cast<char>(std::toupper(static_cast<unsigned char>(ch)));
+    return u == w;
+  };
+  for (;;) {
+    if (is_word(pos, "INNER") && is_kw(pos + 1, "JOIN")) ++pos;
+    else if (is_word(pos, "LEFT") && is_kw(pos + 1, "JOIN")) ++pos;
+    else if (is_word(pos, "LEFT") && is_word(pos + 1, "OUTER") && is_kw(pos + 2, "JOIN")) pos += 2;
+    if (!is_kw(pos, "JOIN")) break;
     ++pos;
     if (pos >= end || tokens[pos].type != TokenType::Identifier)
       throw std::runtime_error("Expected table name after JOIN" + where_at(at(pos)));
     JoinClause j;
     j.table = tokens[pos++].value;
     expect("ON");
-    const size_t stop = until({"WHERE", "GROUP", "ORDER", "HAVING", "JOIN", "LIMIT", "OFFSET"});
+    size_t stop = until({"WHERE", "GROUP", "ORDER", "HAVING", "JOIN", "LIMIT", "OFFSET"});
+    if (is_kw(stop, "JOIN")) {  // the next JOIN's own INNER / LEFT [OUTER] is not part of this condition
+      if (stop >= pos + 2 && is_word(stop - 1, "OUTER") && is_word(stop - 2, "LEFT")) stop -= 2;
+      else if (stop >= pos + 1 && (is_word(stop - 1, "INNER") || is_word(stop - 1, "LEFT"))) stop -= 1;
+    }
     j.condition = parse_in_query(tokens, pos, stop);
     pos = stop;
     q.joins.push_back(std::move(j));

@@ -574,4 +574,199 @@ WindowedPlan plan_sql_windowed(const std::string &sql, const NameSet &cols) {
   return p;
 }
 
+// -------------------------------------------------------- query_sql_joined
+const char *const kJoinRightPrefix = "wxr_";
+
+namespace {
+// Resolves every column reference of a tree against the two tables and
+// rewrites it to the name the execution layer sees: the bare column for the
+// left table, kJoinRightPrefix + column for the right one.
+struct JoinScope {
+  const std::string &left_name;
+  const NameSet &left_cols;
+  const std::string &right_name;
+  const NameSet &right_cols;
+  bool left = false, right = false;  // which sides the trees resolved so far name
+
+  void resolve(VariableNode &v) {
+    const std::string written = v.name;
+    const auto dot = written.find('.');
+    bool to_right;
+    std::string col = written;
+    if (dot != std::string::npos) {
+      const std::string q = written.substr(0, dot);
+      col = written.substr(dot + 1);
+      if (q == left_name && left_cols.count(col)) to_right = false;
+      else if (q == right_name && right_cols.count(col)) to_right = true;
+      else throw std::runtime_error("Unknown column: " + written);
+    } else {
+      const bool l = left_cols.count(col) != 0, r = right_cols.count(col) != 0;
+      if (l && r) throw std::runtime_error("Ambiguous column: " + written);
+      if (!l && !r) throw std::runtime_error("Unknown column: " + written);
+      to_right = r;
+    }
+    v.name = to_right ? kJoinRightPrefix + col : col;
+    (to_right ? right : left) = true;
+  }
+  void resolve(ASTNode *n) {
+    if (!n) return;
+    if (auto v = dynamic_cast<VariableNode *>(n)) {
+      resolve(*v);
+    } else if (auto b = dynamic_cast<BinaryOpNode *>(n)) {
+      resolve(b->left.get());
+      resolve(b->right.get());
+    } else if (auto f = dynamic_cast<FunctionCallNode *>(n)) {
+      for (auto &a : f->args) resolve(a.get());
+    } else if (!dynamic_cast<ConstantNode *>(n)) {
+      // an aggregate or a window item inside an expression: its columns would go unresolved
+      throw std::runtime_error("aggregates and window functions are not supported inside a joined expression");
+    }
+  }
+};
+
+// the column a bare reference names, without its qualifier
+std::string joined_name(const ASTNode *n, size_t pos) {
+  if (auto v = dynamic_cast<const VariableNode *>(n)) {
+    const auto dot = v->name.find('.');
+    return dot == std::string::npos ? v->name : v->name.substr(dot + 1);
+  }
+  return column_name(n, pos);
+}
+
+const char *const kJoinCondition = "JOIN condition must be <left expression> = <right column>";
+}  // namespace
+
+bool join_is_left_outer(const std::vector<Token> &tokens, size_t join_index) {
+  auto word = [&](size_t p, const char *w) {
+    if (tokens[p].type != TokenType::Identifier) return false;
+    std::string u = tokens[p].value;
+    for (char &ch : u) ch = static_cast<char>(std::toupper(static_cast<unsigned char>(ch)));
+    return u == w;
+  };
+  size_t seen = 0;
+  for (size_t i = 0; i < tokens.size(); ++i) {
+    if (tokens[i].type != TokenType::Keyword || tokens[i].value != "JOIN" || seen++ != join_index) continue;
+    return (i >= 1 && word(i - 1, "LEFT")) || (i >= 2 && word(i - 1, "OUTER") && word(i - 2, "LEFT"));
+  }
+  return false;
+}
+
+JoinedPlan plan_sql_joined(const std::string &sql, const NameSet &left_cols, const std::string &right_name,
+                           const NameSet &right_cols) {
+  return plan_sql_joined(sql, left_cols,
+                         [&](const std::string &name) { return name == right_name ? &right_cols : nullptr; });
+}
+
+JoinedPlan plan_sql_joined(const std::string &sql, const NameSet &left_cols, const JoinTables &right_cols_of) {
+  std::vector<Token> tokens;
+  QueryAST ast;
+  try {
+    tokens = tokenize(sql);
+    ast = parse_query(tokens);
+  } catch (const std::exception &e) {
+    throw std::runtime_error(std::string("Failed to parse SQL: ") + e.what());
+  }
+  if (ast.select_list.empty()) throw std::runtime_error("Empty SELECT list");
+  if (ast.joins.empty()) throw std::runtime_error("query_sql_joined needs a JOIN clause (use query_sql_table)");
+  if (ast.joins.size() > 1) throw std::runtime_error("a second JOIN is not supported by query_sql_joined");
+  if (ast.group_by) throw std::runtime_error("GROUP BY is not supported by query_sql_joined");
+  if (ast.having) throw std::runtime_error("HAVING is not supported by query_sql_joined");
+  if (ast.distinct) throw std::runtime_error("DISTINCT is not supported by query_sql_joined");
+  if (ast.order_by) throw std::runtime_error("ORDER BY is not supported by query_sql_joined (the result is in row order)");
+  for (const auto &e : ast.select_list)
+    if (is_agg(e.get()))
+      throw std::runtime_error("aggregates are not supported by query_sql_joined (plain expressions only)");
+  for (const auto &e : ast.select_list)
+    if (is_window(e.get())) throw std::runtime_error("window functions are not supported by query_sql_joined");
+  JoinClause &j = ast.joins[0];
+  const NameSet *right = right_cols_of(j.table);
+  if (!right) throw std::runtime_error("Unknown table: " + j.table + " (attach it first)");
+  const NameSet &right_cols = *right;
+  if (ast.select_list.size() > WarpDB::kMaxSelectExprs)
+    throw std::runtime_error(kTooManyItems + std::to_string(WarpDB::kMaxSelectExprs) + " expressions");
+  JoinedPlan p;
+  p.right_table = j.table;
+  p.left_outer = join_is_left_outer(tokens, 0);
+  // the ON condition: <left expression> = <right column>, either way round
+  auto *on = dynamic_cast<BinaryOpNode *>(j.condition.get());
+  if (!on || (on->op != "==" && on->op != "=")) throw std::runtime_error(kJoinCondition);
+  JoinScope ls{ast.from_table, left_cols, j.table, right_cols}, rs{ast.from_table, left_cols, j.table, right_cols};
+  try {
+    ls.resolve(on->left.get());
+    rs.resolve(on->right.get());
+  } catch (const std::exception &e) {
+    throw std::runtime_error(std::string("JOIN condition: ") + e.what());
+  }
+  // which tables each side names: {left table, right table}
+  bool key_names[2] = {ls.left, ls.right}, col_names[2] = {rs.left, rs.right};
+  ASTNode *key_side = on->left.get(), *col_side = on->right.get();
+  if (dynamic_cast<VariableNode *>(on->left.get()) && ls.right && !ls.left && !rs.right) {
+    std::swap(key_side, col_side);
+    std::swap(key_names, col_names);
+  }
+  auto *rcol = dynamic_cast<VariableNode *>(col_side);
+  if (!rcol || !col_names[1] || col_names[0] || key_names[1]) throw std::runtime_error(kJoinCondition);
+  p.left_key = key_side->to_cuda_expr();
+  p.right_key = rcol->name.substr(std::string(kJoinRightPrefix).size());
+  JoinScope scope{ast.from_table, left_cols, j.table, right_cols};
+  for (size_t i = 0; i < ast.select_list.size(); ++i) {
+    p.names.push_back(joined_name(ast.select_list[i].get(), i));
+    try {
+      scope.resolve(ast.select_list[i].get());
+    } catch (const std::exception &e) {
+      throw std::runtime_error(std::string("SELECT clause: ") + e.what());
+    }
+    p.lowered.push_back(ast.select_list[i]->to_cuda_expr());
+  }
+  if (ast.where) {
+    try {
+      scope.resolve(ast.where->get());
+    } catch (const std::exception &e) {
+      throw std::runtime_error(std::string("WHERE clause: ") + e.what());
+    }
+  }
+  p.cond = lowered_where(ast);
+  p.window = Window(ast);
+  return p;
+}
+
+JoinedPlan plan_join(const std::string &left_name, const NameSet &left_cols, const std::string &right_name,
+                     const NameSet &right_cols, const std::string &left_key, const std::string &right_key,
+                     const std::vector<std::string> &exprs, const std::string &where, bool left_outer) {
+  if (exprs.empty()) throw std::runtime_error("Empty SELECT list");
+  if (exprs.size() > WarpDB::kMaxSelectExprs)
+    throw std::runtime_error("query_join takes at most " + std::to_string(WarpDB::kMaxSelectExprs) + " expressions");
+  JoinedPlan p;
+  p.right_table = right_name;
+  p.left_outer = left_outer;
+  if (blank(left_key)) throw std::runtime_error("Empty query expression");
+  const ASTNodePtr key = parse_plain(left_key);
+  JoinScope ks{left_name, left_cols, right_name, right_cols};
+  ks.resolve(key.get());
+  if (ks.right || is_agg(key.get())) throw std::runtime_error(kJoinCondition);
+  p.left_key = key->to_cuda_expr();
+  const auto dot = right_key.find('.');
+  p.right_key = dot != std::string::npos && right_key.substr(0, dot) == right_name ? right_key.substr(dot + 1) : right_key;
+  if (!right_cols.count(p.right_key)) throw std::runtime_error("Unknown column: " + right_key);
+  JoinScope scope{left_name, left_cols, right_name, right_cols};
+  for (size_t i = 0; i < exprs.size(); ++i) {
+    if (blank(exprs[i])) throw std::runtime_error("Empty query expression");
+    const ASTNodePtr ex = parse_plain(exprs[i]);
+    if (is_agg(ex.get())) throw std::runtime_error("query_join takes plain expressions, not aggregates");
+    p.names.push_back(joined_name(ex.get(), i));
+    scope.resolve(ex.get());
+    p.lowered.push_back(ex->to_cuda_expr());
+  }
+  if (!blank(where)) {
+    try {
+      const ASTNodePtr cx = parse_expression(tokenize(where));
+      scope.resolve(cx.get());
+      p.cond = cx->to_cuda_expr();
+    } catch (const std::exception &err) {
+      throw std::runtime_error(std::string("Failed to parse WHERE clause: ") + err.what());
+    }
+  }
+  return p;
+}
+
 }  // namespace warpdb

@@ -218,6 +218,39 @@ struct WindowedPlan {
 };
 WindowedPlan plan_sql_windowed(const std::string &sql, const NameSet &cols);
 
+// query_sql_joined: "SELECT items FROM t [INNER] JOIN u ON c [WHERE w] [LIMIT n]
+// [OFFSET m]" (or LEFT [OUTER] JOIN), each item a plain expression over the
+// columns of both tables.  c is <expression over t's columns> = <bare column
+// of u>, with = or ==, either way round.  A name may be qualified with its
+// table (t.price, u.rate); an unqualified name found in both tables is
+// ambiguous.  The lowered texts name u's columns with the prefix
+// kJoinRightPrefix, so equal names in the two tables never collide.
+extern const char *const kJoinRightPrefix;  // "wxr_"
+struct JoinedPlan {
+  std::string right_table;  // u
+  bool left_outer = false;
+  std::string left_key;     // lowered, over t's columns
+  std::string right_key;    // u's column, by its own name
+  std::vector<std::string> names, lowered;
+  std::string cond;
+  Window window;
+};
+JoinedPlan plan_sql_joined(const std::string &sql, const NameSet &left_cols, const std::string &right_name,
+                           const NameSet &right_cols);
+// The same with the right table looked up by the name the query gives it
+// (null: no such table), so that the query is parsed once.
+using JoinTables = std::function<const NameSet *(const std::string &name)>;
+JoinedPlan plan_sql_joined(const std::string &sql, const NameSet &left_cols, const JoinTables &right_cols_of);
+// Whether the join_index-th JOIN of a token list is LEFT [OUTER] JOIN.  The
+// AST cannot say: JoinClause keeps its size (include/warpdb/expression.hpp).
+bool join_is_left_outer(const std::vector<Token> &tokens, size_t join_index);
+// query_join: the same plan from its parts (left_key an expression over the
+// left columns, right_key a column of the right table, exprs and where over
+// both; names unqualified or qualified with `left_name` / `right_name`).
+JoinedPlan plan_join(const std::string &left_name, const NameSet &left_cols, const std::string &right_name,
+                     const NameSet &right_cols, const std::string &left_key, const std::string &right_key,
+                     const std::vector<std::string> &exprs, const std::string &where, bool left_outer);
+
 // The groups of a GroupedPlan: keys and counts (shared), one set of
 // aggregates per slot.  run.order after finish() as in GroupRun.
 struct GroupedRun {

@@ -59,6 +59,12 @@ py::tuple table_arrays(const warpdb::ResultTable &t) {
   for (const auto &c : t.columns) cols.append(py::array_t<float>(static_cast<py::ssize_t>(c.size()), c.data()));
   return py::make_tuple(t.names, cols, py::array_t<int64_t>(static_cast<py::ssize_t>(t.rows.size()), t.rows.data()));
 }
+// a joined result: table_arrays' three and the matched right rows
+py::tuple joined_arrays(const warpdb::ResultTable &t) {
+  py::tuple base = table_arrays(t);
+  return py::make_tuple(base[0], base[1], base[2],
+                        py::array_t<int64_t>(static_cast<py::ssize_t>(t.right_rows.size()), t.right_rows.data()));
+}
 
 py::tuple device_capsules(ArrowDeviceArray *arr, ArrowSchema *schema) {
   // named as the Arrow PyCapsule interface names device arrays
@@ -211,6 +217,43 @@ PYBIND11_MODULE(pywarpdb, m) {
           py::arg("sql"),
           "SELECT key / aggregates of any value expressions ... GROUP BY key [HAVING] [ORDER BY] [LIMIT] [OFFSET] "
           "(fused grouped passes of up to four value expressions) -> (names, [float32 arrays]).")
+      .def(
+          "attach",
+          [](WarpDB &db, const std::string &name, const std::string &path, const std::vector<DataType> &schema) {
+            py::gil_scoped_release nogil;
+            db.attach(name, path, schema);
+          },
+          py::arg("name"), py::arg("path"), py::arg("schema") = std::vector<DataType>{},
+          "Load a second table (.csv / .json) into HBM of the same device under `name`, for query_join / "
+          "query_sql_joined.")
+      .def(
+          "query_join",
+          [](WarpDB &db, const std::string &name, const std::string &left_key, const std::string &right_key,
+             const std::vector<std::string> &exprs, const std::string &where, bool left_outer) {
+            warpdb::ResultTable t;
+            {
+              py::gil_scoped_release nogil;
+              t = db.query_join(name, left_key, right_key, exprs, where,
+                                left_outer ? WarpDB::JoinType::Left : WarpDB::JoinType::Inner);
+            }
+            return joined_arrays(t);
+          },
+          py::arg("name"), py::arg("left_key"), py::arg("right_key"), py::arg("exprs"), py::arg("where") = "",
+          py::arg("left_outer") = false,
+          "PK-FK equi-join with an attached table: (names, columns, left row ids, matched right rows; -1 unmatched).")
+      .def(
+          "query_sql_joined",
+          [](WarpDB &db, const std::string &sql) {
+            warpdb::ResultTable t;
+            {
+              py::gil_scoped_release nogil;
+              t = db.query_sql_joined(sql);
+            }
+            return joined_arrays(t);
+          },
+          py::arg("sql"),
+          "SELECT items FROM t [INNER | LEFT [OUTER]] JOIN u ON <left expression> = <right column> [WHERE c] [LIMIT n] "
+          "[OFFSET m]: (names, columns, left row ids, matched right rows).")
       .def(
           "query_sql_windowed",
           [](WarpDB &db, const std::string &sql) {

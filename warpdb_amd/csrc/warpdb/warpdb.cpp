@@ -18,10 +18,12 @@
 #include <deque>
 #include <exception>
 #include <fstream>
+#include <map>
 #include <mutex>
 #include <sstream>
 #include <stdexcept>
 #include <thread>
+#include <unordered_map>
 
 #include "warpdb/internal.hpp"
 #include "warpdb/multi_gpu_utils.hpp"
@@ -142,7 +144,29 @@ WarpDB::WarpDB(const std::string &filepath, const std::vector<DataType> &schema,
   table_ = upload_to_gpu(host_table_, device);
 }
 
-WarpDB::~WarpDB() { free_table(table_); }
+// The attached tables of every WarpDB (attach()), by name.  Kept outside the
+// object (warpdb.hpp says why).  Each table is held by shared pointers whose
+// deleter frees its device memory: a running join keeps the table it started
+// with, whatever attach() or the destructor do meanwhile.
+namespace {
+using Attached = std::map<std::string, std::shared_ptr<const Table>>;
+std::mutex g_attached_mu;
+std::unordered_map<const WarpDB *, Attached> g_attached;
+}  // namespace
+
+WarpDB::~WarpDB() {
+  Attached mine;
+  {
+    std::lock_guard<std::mutex> lk(g_attached_mu);
+    auto it = g_attached.find(this);
+    if (it != g_attached.end()) {
+      mine = std::move(it->second);
+      g_attached.erase(it);
+    }
+  }
+  mine.clear();  // frees the tables no query still holds
+  free_table(table_);
+}
 
 std::vector<float> WarpDB::query(const std::string &expr) {
   const DeviceBuffer out = project_dense(table_, warpdb::lower_query(expr, names_of(table_)));
@@ -684,6 +708,94 @@ WarpDB::ResultTable WarpDB::query_sql_windowed(const std::string &sql) {
   out.rows = download(ptr<int64_t>(idx), keep, dev);
   p.window.apply(out.rows);
   return out;
+}
+
+// ------------------------------------------------------------------- joins
+// One planned join of `left` with the attached table `right`.
+static warpdb::ResultTable join_run(const Table &table_, const Table *right, const warpdb::JoinedPlan &p) {
+  if (!right) throw std::runtime_error("Unknown table: " + p.right_table + " (attach it first)");
+  const int dev = table_.device;
+  const int64_t n = table_.num_rows;
+  const size_t m = p.lowered.size();
+  // the right table under the planner's prefix, so equal names in the two tables never collide
+  WxTableView lv(table_), rv(*right);
+  for (size_t c = 0; c < rv.names.size(); ++c) rv.names[c] = warpdb::kJoinRightPrefix + rv.names[c];
+  for (size_t c = 0; c < rv.cols.size(); ++c) rv.cols[c].name = rv.names[c].c_str();
+  const std::string rkey = warpdb::kJoinRightPrefix + p.right_key;
+  std::vector<DeviceBuffer> vals;
+  std::vector<float *> dst;
+  std::vector<const char *> ex;
+  for (size_t j = 0; j < m; ++j) {
+    vals.emplace_back(dev, sizeof(float) * static_cast<size_t>(n));
+    dst.push_back(ptr<float>(vals[j]));
+    ex.push_back(p.lowered[j].c_str());
+  }
+  DeviceBuffer idx(dev, sizeof(int64_t) * static_cast<size_t>(n)), rrow(dev, sizeof(int32_t) * static_cast<size_t>(n));
+  wx_launch L = sync_launch(dev);
+  int64_t count = 0;
+  wx_call(wx_join_select, &lv.table, &rv.table, p.left_key.c_str(), rkey.c_str(),
+          static_cast<int32_t>(p.left_outer ? WX_JOIN_LEFT : WX_JOIN_INNER), ex.data(), static_cast<int32_t>(m),
+          p.cond.c_str(), &L, dst.data(), idx.ptr, 8, static_cast<int64_t>(0), ptr<int32_t>(rrow), nullptr, &count);
+  // row order: only the first OFFSET + LIMIT rows are downloaded
+  const int64_t keep = std::min(count, p.window.rows_needed(n));
+  warpdb::ResultTable out;
+  out.names = p.names;
+  for (size_t j = 0; j < m; ++j) {
+    out.columns.push_back(download_result(dst[j], keep, dev));
+    p.window.apply(out.columns.back());
+  }
+  out.rows = download(ptr<int64_t>(idx), keep, dev);
+  p.window.apply(out.rows);
+  for (int32_t r : download(ptr<int32_t>(rrow), keep, dev)) out.right_rows.push_back(r);
+  p.window.apply(out.right_rows);
+  return out;
+}
+
+std::shared_ptr<const Table> WarpDB::attached(const std::string &name) const {
+  std::lock_guard<std::mutex> lk(g_attached_mu);
+  auto it = g_attached.find(this);
+  if (it == g_attached.end()) return nullptr;
+  auto t = it->second.find(name);
+  return t == it->second.end() ? nullptr : t->second;
+}
+
+void WarpDB::attach(const std::string &name, const std::string &filepath, const std::vector<DataType> &schema) {
+  if (warpdb::blank(name)) throw std::runtime_error("attach needs a table name");
+  const std::string ext = lower_ext(filepath);
+  HostTable host;
+  if (ext == "csv") host = load_csv_to_host(filepath, schema);
+  else if (ext == "json") host = load_json_to_host(filepath);
+  else throw std::runtime_error("Unsupported file format: " + filepath);
+  std::shared_ptr<const Table> t(new Table(upload_to_gpu(host, table_.device)), [](const Table *p) {
+    free_table(const_cast<Table &>(*p));  // created non-const above
+    delete p;
+  });
+  std::lock_guard<std::mutex> lk(g_attached_mu);
+  g_attached[this][name] = std::move(t);  // a table attached earlier under the name goes when its last query ends
+}
+
+WarpDB::ResultTable WarpDB::query_join(const std::string &name, const std::string &left_key,
+                                       const std::string &right_key, const std::vector<std::string> &exprs,
+                                       const std::string &where, JoinType join_type) {
+  const std::shared_ptr<const Table> right = attached(name);
+  if (!right) throw std::runtime_error("Unknown table: " + name + " (attach it first)");
+  // this table has no name of its own outside SQL: only the attached one qualifies
+  const warpdb::JoinedPlan p = warpdb::plan_join("", names_of(table_), name, names_of(*right), left_key, right_key,
+                                                 exprs, where, join_type == JoinType::Left);
+  return join_run(table_, right.get(), p);
+}
+
+WarpDB::ResultTable WarpDB::query_sql_joined(const std::string &sql) {
+  // the JOIN's table picks the attached table while the planner parses the query (once)
+  std::shared_ptr<const Table> right;
+  warpdb::NameSet right_cols;
+  const warpdb::JoinedPlan p = warpdb::plan_sql_joined(sql, names_of(table_), [&](const std::string &name) {
+    right = attached(name);
+    if (!right) return static_cast<const warpdb::NameSet *>(nullptr);
+    right_cols = names_of(*right);
+    return static_cast<const warpdb::NameSet *>(&right_cols);
+  });
+  return join_run(table_, right.get(), p);
 }
 
 void WarpDB::query_arrow_sql_windowed(const std::string &sql, ArrowArray *out_array, ArrowSchema *out_schema) {

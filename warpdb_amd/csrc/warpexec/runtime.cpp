@@ -317,6 +317,9 @@ void check_errors(Workspace &w) {
   if (bits & WX_DEVERR_INTERNAL_KEY)
     fail(WX_ERR_INTERNAL, "GROUP BY consistency check failed (a key outside its planned range, a work-item "
                           "overflow, or row counts that disagree between passes)");
+  if (bits & WX_DEVERR_JOIN_PROBE)
+    fail(WX_ERR_INTERNAL, "JOIN: table consistency check failed (a probe walked the whole hash table without meeting an empty "
+                          "slot, or the build met a key outside the key range it had found)");
   fail(WX_ERR_INTERNAL, "device error bits set");
 }
 

@@ -186,6 +186,52 @@ int32_t wx_window_tile_rows(int32_t n_outputs, int32_t n_items, int32_t search) 
   }
 }
 
+wx_status wx_join_select(const wx_table *left, const wx_table *right, const char *left_key_expr,
+                         const char *right_key_col, int32_t join_type, const char *const *exprs, int32_t n_exprs,
+                         const char *cond, const wx_launch *launch_, float *const *d_out_vals, void *d_out_idx,
+                         int32_t idx_bytes, int64_t row_base, int32_t *d_out_right_row, int64_t *d_count,
+                         int64_t *h_count, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    do_join_select(left, right, left_key_expr, right_key_col, join_type, exprs, n_exprs, cond, launch_, d_out_vals,
+                   d_out_idx, idx_bytes, row_base, d_out_right_row, d_count, h_count);
+  });
+}
+
+wx_status wx_prepare_join(const wx_table *left, const wx_table *right, const char *left_key_expr,
+                          const char *right_key_col, int32_t join_type, const char *const *exprs, int32_t n_exprs,
+                          const char *cond, const wx_launch *launch_, int32_t with_right_row, int32_t form, char *err,
+                          size_t errlen) {
+  return guarded(err, errlen, [&] {
+    do_prepare_join(left, right, left_key_expr, right_key_col, join_type, exprs, n_exprs, cond, launch_,
+                    with_right_row, form);
+  });
+}
+
+int32_t wx_join_tile_rows(int32_t n_outputs, int32_t form, int32_t with_right_row) {
+  if (with_right_row != 0 && with_right_row != 1) return 0;
+  try {
+    Spec spec;
+    join_geometry(spec, n_outputs, form, with_right_row != 0);
+    return (int32_t)(spec.dwaves * 64 * 4 * spec.groups);
+  } catch (const WxError &) {
+    return 0;
+  }
+}
+
+wx_status wx_join_plan(int64_t n_right, int32_t key_min, int32_t key_max, int32_t *form, int32_t *log2_capacity,
+                       char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    const JoinPlan p = join_plan(n_right, key_min, key_max);
+    if (form) *form = p.form;
+    if (log2_capacity) *log2_capacity = p.log2cap;
+  });
+}
+
+int32_t wx_join_hash_slot(int32_t key, int32_t log2_capacity) {
+  if (log2_capacity < WX_JOIN_MIN_LOG2CAP || log2_capacity > 27) return -1;
+  return (int32_t)(((uint32_t)key * WX_JOIN_HASH_MUL) >> (32 - log2_capacity));
+}
+
 wx_status wx_group_partials(const wx_table *table, const char *val_expr, const char *key_expr, const char *cond,
                             const wx_launch *launch_, int32_t key_window_lo, double *d_window, int64_t capacity,
                             int32_t *d_keys, double *d_sums, int64_t *d_counts, int64_t *d_n_extra,

@@ -26,6 +26,7 @@
 #include "../kernels/wx_args.h"
 #include "../kernels/wx_select_args.h"
 #include "../kernels/wx_window_args.h"
+#include "../kernels/wx_join_args.h"
 #include "../kernels/wx_gather_args.h"
 #include "../kernels/wx_radix_args.h"
 #include "../kernels/wx_group_multi_args.h"
@@ -146,6 +147,9 @@ struct Workspace {
   Buf wn_keys, wn_cnts, wn_ng, wn_planes;
   Buf wn_sums[WX_WIN_MAX_VALUES], wn_mins[WX_WIN_MAX_VALUES], wn_maxs[WX_WIN_MAX_VALUES];
   int64_t wn_range[2] = {0, 0};  // landing slot of {group count, first | last key} (outlives the copy)
+  // join (wx_join.hip): the build's record, the direct table, the hash table
+  Buf jn_rec, jn_rows, jn_slots;
+  uint32_t jn_host[WX_JOIN_REC_WORDS] = {};  // landing slot of the record (outlives the copy)
   Buf diag;  // WX_DIAG_TIMELINE per-workgroup times
   std::vector<Buf *> bufs;  // every buffer ensure() has allocated: wx_shutdown frees them all
 };
@@ -197,6 +201,15 @@ struct Spec {
   // output j's plain expression (empty for a window item), `key` the partition
   int win_nout = 0, win_mask = 0, win_search = 0;
   std::vector<std::string> win_exprs;
+  // join probe (wx_join.hip): outputs of the launch (0 = n/a), direct (0) or
+  // hash (1) form, inner (0) or left outer (1), which outputs name a right
+  // column, whether the WHERE does, whether the matched right row is staged;
+  // join_exprs[j] is output j's expression, `key` the left key, rcols the
+  // referenced columns of the right table (table_index: into the right table)
+  int join_nout = 0, join_form = 0, join_left = 0, join_rmask = 0, join_condr = 0, join_rrow = 0;
+  std::vector<std::string> join_exprs;
+  std::string join_cond;  // the WHERE (`cond` stays empty: see Spec::source)
+  std::vector<UsedCol> rcols;
   std::string custom;
   std::string extra;  // diagnostic -D list from $WARPDB_EXTRA_DEFINES
 
@@ -214,6 +227,7 @@ void compact_geometry(Spec &spec);
 bool compact_ticket_sched();
 void select_geometry(Spec &spec, int nout);
 void window_geometry(Spec &spec, int nout, int n_items, bool search);
+void join_geometry(Spec &spec, int nout, int form, bool right_row);
 void gather_geometry(Spec &spec, int nout);
 std::string default_arch();
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
@@ -248,6 +262,24 @@ Spec window_spec(const wx_table *t, const char *const *exprs, int32_t n_out, int
 Spec window_table_spec();
 void check_window_args(const wx_table *t, const char *const *exprs, int32_t n_exprs, const wx_window_item *items,
                        int32_t n_items, const char *part_expr, const char *cond);
+// The join family.  JoinNames: what a call's expressions reference in each
+// table, checked without a device (check_join_args); join_spec: one launch of
+// the probe over outputs [first, first + n_out) of the call.
+struct JoinNames {
+  std::vector<UsedCol> left, right;  // over the whole call
+  int right_key = -1;                // index of right_key_col in the right table
+};
+JoinNames check_join_args(const wx_table *left, const wx_table *right, const char *left_key_expr,
+                          const char *right_key_col, int32_t join_type, const char *const *exprs, int32_t n_exprs,
+                          const char *cond);
+Spec join_spec(const wx_table *left, const wx_table *right, const char *const *exprs, int32_t n_out, int form,
+               bool left_outer, bool right_row, const char *left_key_expr, const char *cond, const wx_launch &L);
+Spec join_table_spec();
+struct JoinPlan {
+  int form = WX_JOIN_FORM_HASH;
+  int log2cap = WX_JOIN_MIN_LOG2CAP;  // hash form: log2 of the slots (0 in the direct form)
+};
+JoinPlan join_plan(int64_t n_right, int32_t key_min, int32_t key_max);
 Spec util_spec(const std::string &more = "");
 
 // runtime.cpp
@@ -339,6 +371,15 @@ void do_window_select(const wx_table *t, const char *const *exprs, int32_t n_exp
                       int64_t row_base, int64_t *d_count, int64_t *h_count);
 void do_prepare_window(const wx_table *t, const char *const *exprs, int32_t n_exprs, const wx_window_item *items,
                        int32_t n_items, const char *part_expr, const char *cond, const wx_launch *Lp, int32_t search);
+
+// join.cpp
+void do_join_select(const wx_table *left, const wx_table *right, const char *left_key_expr, const char *right_key_col,
+                    int32_t join_type, const char *const *exprs, int32_t n_exprs, const char *cond,
+                    const wx_launch *Lp, float *const *d_out_vals, void *d_out_idx, int32_t idx_bytes,
+                    int64_t row_base, int32_t *d_out_right_row, int64_t *d_count, int64_t *h_count);
+void do_prepare_join(const wx_table *left, const wx_table *right, const char *left_key_expr, const char *right_key_col,
+                     int32_t join_type, const char *const *exprs, int32_t n_exprs, const char *cond,
+                     const wx_launch *Lp, int32_t with_right_row, int32_t form);
 
 // group.cpp
 struct KeyRange {
