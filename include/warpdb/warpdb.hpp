@@ -180,6 +180,15 @@ class WarpDB {
   // table.  GROUP BY, HAVING, DISTINCT, ORDER BY, aggregates, window items
   // and a second JOIN are refused.
   ResultTable query_sql_joined(const std::string &sql);
+  // SELECT items FROM t [INNER] JOIN u ON <expression over t> = <column of u>
+  // [WHERE c] GROUP BY k [HAVING h] [ORDER BY o [ASC|DESC]] [LIMIT n]
+  // [OFFSET m]: query_sql_grouped over the rows the inner join keeps, in one
+  // pass per four value expressions that probes u and aggregates without
+  // writing a joined row.  Items are the key or SUM / AVG / COUNT / MIN / MAX of
+  // any expression; expressions, the key and WHERE are over the columns of
+  // both tables.  LEFT JOIN is refused (an unmatched row would need NULL-aware
+  // aggregates), as are a second JOIN, DISTINCT and window items.
+  ResultTable query_sql_joined_grouped(const std::string &sql);
 
   const Table &table() const { return table_; }
   const HostTable &host_table() const { return host_table_; }

@@ -531,6 +531,53 @@ wx_status wx_join_plan(int64_t n_right, int32_t key_min, int32_t key_max, int32_
  * kernels compute it; -1 when log2_capacity is outside 6 .. 27. */
 int32_t wx_join_hash_slot(int32_t key, int32_t log2_capacity);
 
+/* JOIN under GROUP BY: wx_group_agg_multi over exactly the rows
+ * wx_join_select(left, right, .., WX_JOIN_INNER, .., cond) keeps, in one pass
+ * that probes the right table and adds into the group accumulators, so no
+ * joined row is written.  Groups of (int)group_key_expr, ascending, one count
+ * per group; val_exprs (1 .. WX_GROUP_MAX_VALUES), group_key_expr and cond are
+ * lowered C text over the columns of both tables and may mix them.  Sums are
+ * of (float) values in double; MIN / MAX follow wx_group_agg (NaN skipped, NaN
+ * when none qualifies, -0.0 returned as +0.0).  The nullable output pointers
+ * say what is computed, as in wx_group_agg_multi: a value with neither a sum,
+ * a minimum nor a maximum requested returns WX_ERR_INVALID.  key_window_lo,
+ * capacity, d_n_groups / h_n_groups and WX_ERR_CAPACITY (h_n_groups still
+ * holds the number of groups found) behave as in wx_group_agg_multi; the
+ * window stays at key_window_lo.
+ * The tables, left_key_expr, right_key_col and the column rules are
+ * wx_join_select's (16 columns per table, "column <x> is in both tables",
+ * left_key_expr over left columns only, a bare unique INT32 right key, at
+ * most 2^26 right rows; a duplicate key fails before the grouped pass runs).
+ * WX_JOIN_LEFT returns WX_ERR_UNSUPPORTED ("LEFT JOIN under GROUP BY is not
+ * supported (an unmatched row needs NULL-aware aggregates)"): the engine has
+ * no NULLs and keeps one count per group.  WX_F_ROW_ORDER returns
+ * WX_ERR_UNSUPPORTED.  With no right rows or no left rows the result is zero
+ * groups.
+ * Run: the table build of wx_join_select (two synchronisations), then one
+ * launch of wx_join_group and the finalize; with WX_F_TIME the grouped pass
+ * alone is timed. */
+wx_status wx_join_group_agg(const wx_table *left, const wx_table *right, const char *left_key_expr,
+                            const char *right_key_col, int32_t join_type, const char *const *val_exprs, int32_t n_vals,
+                            const char *group_key_expr, const char *cond, const wx_launch *launch,
+                            int32_t key_window_lo, int64_t capacity, int32_t *d_keys, double *const *d_sums,
+                            int64_t *d_counts, float *const *d_mins, float *const *d_maxs, int64_t *d_n_groups,
+                            int64_t *h_n_groups, char *err, size_t errlen);
+/* Build (and cache) the modules wx_join_group_agg would use -- the build
+ * module and the grouped pass for these masks (bit j: value j carries a SUM /
+ * a MIN or MAX) in the direct (form == 0) or the hash (form == 1) form --
+ * without launching (works without a GPU, like wx_prepare). */
+wx_status wx_prepare_join_group(const wx_table *left, const wx_table *right, const char *left_key_expr,
+                                const char *right_key_col, int32_t join_type, const char *const *val_exprs,
+                                int32_t n_vals, uint32_t sum_mask, uint32_t minmax_mask, const char *group_key_expr,
+                                const char *cond, const wx_launch *launch, int32_t form, char *err, size_t errlen);
+/* Threads per workgroup, workgroups per CU and LDS bytes per workgroup of the
+ * grouped pass for n_sums summed and n_minmax MIN / MAX values (0 .. 4 each,
+ * at least one in all) in the direct (0) or the hash (1) form; each output
+ * nullable.  per_cu * lds_bytes never exceeds the 160 KiB of a CU.  Needs no
+ * device. */
+wx_status wx_join_group_geometry(int32_t n_sums, int32_t n_minmax, int32_t form, int32_t *block, int32_t *per_cu,
+                                 int32_t *lds_bytes, char *err, size_t errlen);
+
 /* ORDER BY order_expr [DESC] LIMIT k (1 <= k <= 32) over rows where cond
  * holds; ties broken by ascending row index.  Outputs (device, nullable):
  * order keys, row_base + row indices, and (float)select_expr at those rows

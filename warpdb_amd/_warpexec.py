@@ -94,6 +94,9 @@ EXPORTED_SYMBOLS = (
     "wx_join_tile_rows",
     "wx_join_plan",
     "wx_join_hash_slot",
+    "wx_join_group_agg",
+    "wx_prepare_join_group",
+    "wx_join_group_geometry",
     "wx_group_partials",
     "wx_group_combine",
     "wx_group_partials_slots",
@@ -205,6 +208,11 @@ def load() -> ctypes.CDLL:
                            S],
         "wx_prepare_join": [T, T, E, E, I32, ctypes.POINTER(E), I32, E, L, I32, I32, E, S],
         "wx_join_plan": [I64, I32, I32, ctypes.POINTER(I32), ctypes.POINTER(I32), E, S],
+        "wx_join_group_agg": [T, T, E, E, I32, ctypes.POINTER(E), I32, E, E, L, I32, I64, P, ctypes.POINTER(P), P,
+                              ctypes.POINTER(P), ctypes.POINTER(P), P, pI64, E, S],
+        "wx_prepare_join_group": [T, T, E, E, I32, ctypes.POINTER(E), I32, ctypes.c_uint32, ctypes.c_uint32, E, E, L,
+                                  I32, E, S],
+        "wx_join_group_geometry": [I32, I32, I32, ctypes.POINTER(I32), ctypes.POINTER(I32), ctypes.POINTER(I32), E, S],
         "wx_group_partials": [T, E, E, E, L, I32, P, I64, P, P, P, P, pI64, E, S],
         "wx_group_combine": [P, I32, P, P, P, I64, L, I64, P, P, P, P, pI64, E, S],
         "wx_group_partials_slots": [T, E, E, E, L, I32, P, I32, I32, I32, I64, P, P, P, P, pI64, E, S],
@@ -611,6 +619,56 @@ def join_plan(n_right: int, key_min: int, key_max: int) -> Tuple[int, int]:
 def join_hash_slot(key: int, log2_capacity: int) -> int:
     """The home slot the kernels use for `key` in a table of 1 << log2_capacity slots."""
     return int(load().wx_join_hash_slot(key, log2_capacity))
+
+
+def join_group_agg(left: Table, right: Table, left_key_expr: str, right_key_col: str, val_exprs: Sequence[str],
+                   group_key_expr: str, cond: Optional[str], launch: WxLaunch, key_window_lo: int, capacity: int,
+                   d_keys: int, d_counts: int, d_sums: Optional[Sequence[int]] = None,
+                   d_mins: Optional[Sequence[int]] = None, d_maxs: Optional[Sequence[int]] = None,
+                   d_n_groups: int = 0, want_count: bool = True, join_type: int = JOIN_INNER) -> Optional[int]:
+    """JOIN under GROUP BY: group_agg_multi over the rows join_select (INNER)
+    keeps, in one pass; values, group key and cond are over the columns of
+    both tables.  Outputs as in group_agg_multi; on WX_ERR_CAPACITY the raised
+    error carries the found count in `.count`."""
+    lib = load()
+    err = _err()
+    h = ctypes.c_int64(-1)
+    n = len(val_exprs)
+    st = lib.wx_join_group_agg(ctypes.byref(left.c), ctypes.byref(right.c), _enc(left_key_expr), _enc(right_key_col),
+                               join_type, _expr_array(val_exprs), n, _enc(group_key_expr), _enc(cond),
+                               ctypes.byref(launch), key_window_lo, capacity, d_keys or None, _ptr_array(d_sums, n),
+                               d_counts or None, _ptr_array(d_mins, n), _ptr_array(d_maxs, n), d_n_groups or None,
+                               ctypes.byref(h) if want_count else None, err, len(err))
+    try:
+        _check(st, err)
+    except WarpExecError as e:
+        e.count = h.value
+        raise
+    return h.value if want_count else None
+
+
+def prepare_join_group(left: Table, right: Table, left_key_expr: str, right_key_col: str, val_exprs: Sequence[str],
+                       sum_mask: int, minmax_mask: int, group_key_expr: str, cond: Optional[str] = None,
+                       launch: Optional[WxLaunch] = None, form: int = JOIN_HASH,
+                       join_type: int = JOIN_INNER) -> None:
+    """Compile the modules join_group_agg would use for these masks, in the direct or the hash form (no GPU needed)."""
+    lib = load()
+    err = _err()
+    L = launch or make_launch()
+    _check(lib.wx_prepare_join_group(ctypes.byref(left.c), ctypes.byref(right.c), _enc(left_key_expr),
+                                     _enc(right_key_col), join_type, _expr_array(val_exprs), len(val_exprs), sum_mask,
+                                     minmax_mask, _enc(group_key_expr), _enc(cond), ctypes.byref(L), form, err,
+                                     len(err)), err)
+
+
+def join_group_geometry(n_sums: int, n_minmax: int, form: int = JOIN_HASH) -> Tuple[int, int, int]:
+    """(threads per workgroup, workgroups per CU, LDS bytes per workgroup) of the grouped pass over a join."""
+    lib = load()
+    err = _err()
+    block, per_cu, lds = ctypes.c_int32(-1), ctypes.c_int32(-1), ctypes.c_int32(-1)
+    _check(lib.wx_join_group_geometry(n_sums, n_minmax, form, ctypes.byref(block), ctypes.byref(per_cu),
+                                      ctypes.byref(lds), err, len(err)), err)
+    return block.value, per_cu.value, lds.value
 
 
 def group_partials(table: Table, val_expr: str, key_expr: str, cond: Optional[str], launch: WxLaunch,

@@ -4,7 +4,10 @@
 // (concatenated after wx_common.hip and wx_group_multi_args.h)
 
 // ===========================================================================
-#if WX_OP == WX_OP_GROUP_MULTI
+#if WX_OP == WX_OP_GROUP_MULTI || defined(WX_JOIN_GROUP)
+// (A WX_OP_JOIN_GROUP module, whose prelude defines WX_JOIN_GROUP, takes the
+// accumulator layout, the general-key add and the finalize from here; its
+// streaming kernel is wx_join_group.hip's, and it may carry a single value.)
 // WX_NOUT value expressions (WX_EXPR, WX_EXPR1 .. WX_EXPR3) of the rows of one
 // GROUP BY: the key column is read, the condition evaluated and the bin found
 // once per row.  Two compile-time masks say what a build carries: bit j of
@@ -13,7 +16,7 @@
 // one count per bin serves all values.  Semantics per value are
 // wx_group_sum's: sums of (float) values in double, NaN skipped by MIN / MAX
 // (order-mapped u32, 0 = NaN).
-#if !defined(WX_NOUT) || WX_NOUT < 2 || WX_NOUT > WX_GM_MAX
+#if !defined(WX_NOUT) || WX_NOUT < 1 || WX_NOUT > WX_GM_MAX || (WX_NOUT < 2 && !defined(WX_JOIN_GROUP))
 #error "wx_group_multi takes 2 to 4 value expressions (one is wx_group_sum)"
 #endif
 #if !defined(WX_GM_SUMS) || !defined(WX_GM_MMS)
@@ -32,7 +35,9 @@
 #define WX_GROUP_LEAD 16  // lanes of a wave on one window bin from which they add once (0: off)
 #endif
 
-#if WX_NOUT == 2
+#if WX_NOUT == 1
+#define WX_GM_VALS static_cast<float>(WX_EXPR)
+#elif WX_NOUT == 2
 #define WX_GM_VALS static_cast<float>(WX_EXPR), static_cast<float>(WX_EXPR1)
 #elif WX_NOUT == 3
 #define WX_GM_VALS static_cast<float>(WX_EXPR), static_cast<float>(WX_EXPR1), static_cast<float>(WX_EXPR2)
@@ -93,6 +98,7 @@ __device__ __forceinline__ void wx_gm_hash_add(const WxGroupMultiArgs &a, int ke
   atomicOr(reinterpret_cast<unsigned int *>(&a.ctrs[1]), WX_DEVERR_CAPACITY);
 }
 
+#if WX_OP == WX_OP_GROUP_MULTI
 #undef WX_LBLOCK
 #define WX_LBLOCK (wxgm::BLOCK)
 extern "C" __global__ __launch_bounds__(WX_GM_BLOCK(wxgm::NS, wxgm::NQ)) void wx_group_multi(WxGroupMultiArgs wx_a) {
@@ -183,6 +189,7 @@ extern "C" __global__ __launch_bounds__(WX_GM_BLOCK(wxgm::NS, wxgm::NQ)) void wx
 
 #undef WX_LBLOCK
 #define WX_LBLOCK WX_BLOCK
+#endif
 
 // One 1024-thread block, as wx_group_finalize: sort the general-key entries
 // (in LDS, or read them pre-sorted), merge with the dense window in

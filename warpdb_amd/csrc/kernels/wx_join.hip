@@ -4,7 +4,9 @@
 // expression) and the probe (appended after wx_compact.hip in a
 // WX_OP_COMPACT module whose prelude defines WX_JOIN_NOUT: the lookup and the
 // hooks of the multi-output ordered compaction; wx_compact_multi.hip,
-// appended after it, holds the kernels and says what each hook is).  Every
+// appended after it, holds the kernels and says what each hook is).  The
+// lookup itself is a block of its own that a WX_OP_JOIN_GROUP module takes too
+// (wx_join_group.hip, the probe inside the grouped pass).  Every
 // write to a table is a vector atomic, every read of one an ordinary vector
 // load.
 
@@ -81,7 +83,11 @@ extern "C" __global__ __launch_bounds__(WX_JOIN_BLOCK) void wx_join_build(WxJoin
 #endif
 
 // ===========================================================================
-#if WX_OP == WX_OP_COMPACT && defined(WX_JOIN_NOUT)
+#if (WX_OP == WX_OP_COMPACT && defined(WX_JOIN_NOUT)) || defined(WX_JOIN_GROUP)
+// The lookup and the right-column binding, shared by the probing compaction
+// below and by the grouped pass of wx_join_group.hip (appended after this
+// file in a WX_OP_JOIN_GROUP module, whose prelude defines WX_JOIN_GROUP).
+//
 // The prelude defines, beside the compaction's own:
 //   WX_JOIN_NOUT    outputs of this launch, 1 .. WX_SELECT_MAX_OUT:
 //                   WX_JOIN_EXPR0 .. WX_JOIN_EXPR3 over the columns of both tables
@@ -99,8 +105,6 @@ extern "C" __global__ __launch_bounds__(WX_JOIN_BLOCK) void wx_join_build(WxJoin
 // anything, so the lookup is clamped before it addresses anything: wx_hit
 // says whether the key is in the table, wx_rrow is 0 when it is not, and a
 // right column is loaded only under wx_hit (an unmatched row binds 0).
-static_assert(((unsigned)WX_JOIN_RMASK >> WX_JOIN_NOUT) == 0u, "right-column mask out of range");
-
 #if WX_JOIN_FORM == WX_JOIN_FORM_HASH
 // Linear probing from the home slot; the slot index is masked at every step.
 // At load <= 1/2 an empty slot ends the walk; the walk is bounded by the
@@ -153,6 +157,12 @@ static_assert(((unsigned)WX_JOIN_RMASK >> WX_JOIN_NOUT) == 0u, "right-column mas
 // sides; no load unless the probe hit.
 #define WX_JOIN_BIND_R(name, T, slot) \
   const ::wx::reg<T> name{wx_hit ? static_cast<const T *>(wx_s.rcol[slot])[wx_rrow] : static_cast<T>(0)};
+
+#endif
+
+// ===========================================================================
+#if WX_OP == WX_OP_COMPACT && defined(WX_JOIN_NOUT)
+static_assert(((unsigned)WX_JOIN_RMASK >> WX_JOIN_NOUT) == 0u, "right-column mask out of range");
 
 // An output that names a right column is NaN for the unmatched row a LEFT
 // join keeps (an INNER join keeps none: its outputs are plain).

@@ -1427,6 +1427,23 @@ extern "C" __global__ __launch_bounds__(WX_BLOCK) void wx_sort_prep(WxSortPrepAr
   }
 }
 
+// The general-key entries of a large GROUP BY as sort keys, (key ^ sign) << 32
+// | used-list position, padded with ~0 to npad: what wx_group_gather of the
+// single-value GROUP module does.  It names no expression, so the multi-value
+// GROUP BY and the grouped join sort with this one instead of building a
+// per-query single-value module for it.
+extern "C" __global__ __launch_bounds__(WX_BLOCK) void wx_group_gather_keys(WxGroupGatherArgs a) {
+  const wx_i64 nh = (wx_i64)a.ctrs[0];
+  for (wx_i64 i = (wx_i64)blockIdx.x * WX_BLOCK + threadIdx.x; i < a.npad; i += (wx_i64)gridDim.x * WX_BLOCK) {
+    wx_u64 e = ~0ull;
+    if (i < nh) {
+      const wx_u32 key = (wx_u32)a.h_tag[a.h_used[i]];
+      e = ((wx_u64)(key ^ 0x80000000u) << 32) | (wx_u32)i;
+    }
+    a.keys[i] = e;
+  }
+}
+
 // LDS bitonic steps on one WX_SORT_LDS-element slice per block: for every
 // stage k in [a.k, a.j] (a.j = kend) run all partner distances below
 // WX_SORT_LDS.  The first launch covers k = 2 .. WX_SORT_LDS; afterwards each

@@ -412,26 +412,14 @@ std::vector<std::pair<size_t, size_t>> GroupedPlan::chunks(size_t width) const {
   return c;
 }
 
-GroupedPlan plan_sql_grouped(const std::string &sql, const NameSet &cols) {
-  GroupedPlan p;
-  {
-    SqlPlan checked = checked_sql(sql, cols);  // plan_sql_table's first checks, in its order
-    p.ast = std::move(checked.ast);
-    p.cond = std::move(checked.cond);
-    p.window = checked.window;
-  }
+// The items and the slots of a grouped plan whose ast, key and names are set:
+// select items first, then the aggregates only HAVING / ORDER BY name.  With
+// `cols`, a hidden aggregate's argument is validated against them under its
+// clause's prefix (plan_sql_grouped); a caller that resolved every name
+// already passes none (plan_sql_joined_grouped).
+static void fill_group_slots(GroupedPlan &p, const NameSet *cols) {
   const QueryAST &ast = p.ast;
   const size_t m = ast.select_list.size();
-  for (size_t i = 0; i < m; ++i) p.names.push_back(column_name(ast.select_list[i].get(), i));
-  for (const auto &e : ast.select_list)
-    if (is_window(e.get())) throw std::runtime_error("window functions are not supported by the execution engine");
-  if (!ast.group_by) throw std::runtime_error("query_sql_grouped needs a GROUP BY clause");
-  if (ast.group_by->keys.size() != 1) throw std::runtime_error("GROUP BY supports one key expression");
-  if (ast.distinct) throw std::runtime_error("DISTINCT over a multi-column result is not supported");
-  if (m > WarpDB::kMaxSelectExprs)
-    throw std::runtime_error(kTooManyItems + std::to_string(WarpDB::kMaxSelectExprs) + " expressions");
-  p.key = ast.group_by->keys[0].get();
-
   // the slot of an aggregate's expression, made on first use; COUNT takes none
   auto use = [&](const AggregationNode *a) -> int {
     if (a->agg == AggregationType::Count) return -1;
@@ -463,7 +451,7 @@ GroupedPlan plan_sql_grouped(const std::string &sql, const NameSet &cols) {
   std::function<void(const ASTNode *, const char *)> hidden = [&](const ASTNode *n, const char *ctx) {
     if (auto a = dynamic_cast<const AggregationNode *>(n)) {
       try {
-        validate_ast(a->expr.get(), cols);
+        if (cols) validate_ast(a->expr.get(), *cols);
       } catch (const std::exception &e) {
         throw std::runtime_error(std::string(ctx) + ": " + e.what());
       }
@@ -483,6 +471,29 @@ GroupedPlan plan_sql_grouped(const std::string &sql, const NameSet &cols) {
   }
   // nothing but the key and COUNTs: one summed slot to run on (what is counted, else the key)
   if (p.slots.empty()) p.slots.push_back({(counted ? counted->expr.get() : p.key)->to_cuda_expr(), true, false});
+}
+
+GroupedPlan plan_sql_grouped(const std::string &sql, const NameSet &cols) {
+  GroupedPlan p;
+  {
+    SqlPlan checked = checked_sql(sql, cols);  // plan_sql_table's first checks, in its order
+    p.ast = std::move(checked.ast);
+    p.cond = std::move(checked.cond);
+    p.window = checked.window;
+  }
+  const QueryAST &ast = p.ast;
+  const size_t m = ast.select_list.size();
+  for (size_t i = 0; i < m; ++i) p.names.push_back(column_name(ast.select_list[i].get(), i));
+  for (const auto &e : ast.select_list)
+    if (is_window(e.get())) throw std::runtime_error("window functions are not supported by the execution engine");
+  if (!ast.group_by) throw std::runtime_error("query_sql_grouped needs a GROUP BY clause");
+  if (ast.group_by->keys.size() != 1) throw std::runtime_error("GROUP BY supports one key expression");
+  if (ast.distinct) throw std::runtime_error("DISTINCT over a multi-column result is not supported");
+  if (m > WarpDB::kMaxSelectExprs)
+    throw std::runtime_error(kTooManyItems + std::to_string(WarpDB::kMaxSelectExprs) + " expressions");
+  p.key = ast.group_by->keys[0].get();
+
+  fill_group_slots(p, &cols);
   return p;
 }
 
@@ -587,6 +598,7 @@ struct JoinScope {
   const std::string &right_name;
   const NameSet &right_cols;
   bool left = false, right = false;  // which sides the trees resolved so far name
+  bool aggs = false;                 // descend into an aggregate's argument (the grouped join's items)
 
   void resolve(VariableNode &v) {
     const std::string written = v.name;
@@ -617,6 +629,8 @@ struct JoinScope {
       resolve(b->right.get());
     } else if (auto f = dynamic_cast<FunctionCallNode *>(n)) {
       for (auto &a : f->args) resolve(a.get());
+    } else if (auto a = aggs ? dynamic_cast<AggregationNode *>(n) : nullptr) {
+      resolve(a->expr.get());
     } else if (!dynamic_cast<ConstantNode *>(n)) {
       // an aggregate or a window item inside an expression: its columns would go unresolved
       throw std::runtime_error("aggregates and window functions are not supported inside a joined expression");
@@ -634,6 +648,32 @@ std::string joined_name(const ASTNode *n, size_t pos) {
 }
 
 const char *const kJoinCondition = "JOIN condition must be <left expression> = <right column>";
+
+// The ON condition of a join, <left expression> = <right column> either way
+// round: the lowered left key and the right column by its own name.
+void lower_on(const std::string &left_name, const NameSet &left_cols, JoinClause &j, const NameSet &right_cols,
+              std::string &left_key, std::string &right_key) {
+  auto *on = dynamic_cast<BinaryOpNode *>(j.condition.get());
+  if (!on || (on->op != "==" && on->op != "=")) throw std::runtime_error(kJoinCondition);
+  JoinScope ls{left_name, left_cols, j.table, right_cols}, rs{left_name, left_cols, j.table, right_cols};
+  try {
+    ls.resolve(on->left.get());
+    rs.resolve(on->right.get());
+  } catch (const std::exception &e) {
+    throw std::runtime_error(std::string("JOIN condition: ") + e.what());
+  }
+  // which tables each side names: {left table, right table}
+  bool key_names[2] = {ls.left, ls.right}, col_names[2] = {rs.left, rs.right};
+  ASTNode *key_side = on->left.get(), *col_side = on->right.get();
+  if (dynamic_cast<VariableNode *>(on->left.get()) && ls.right && !ls.left && !rs.right) {
+    std::swap(key_side, col_side);
+    std::swap(key_names, col_names);
+  }
+  auto *rcol = dynamic_cast<VariableNode *>(col_side);
+  if (!rcol || !col_names[1] || col_names[0] || key_names[1]) throw std::runtime_error(kJoinCondition);
+  left_key = key_side->to_cuda_expr();
+  right_key = rcol->name.substr(std::string(kJoinRightPrefix).size());
+}
 }  // namespace
 
 bool join_is_left_outer(const std::vector<Token> &tokens, size_t join_index) {
@@ -687,27 +727,7 @@ JoinedPlan plan_sql_joined(const std::string &sql, const NameSet &left_cols, con
   JoinedPlan p;
   p.right_table = j.table;
   p.left_outer = join_is_left_outer(tokens, 0);
-  // the ON condition: <left expression> = <right column>, either way round
-  auto *on = dynamic_cast<BinaryOpNode *>(j.condition.get());
-  if (!on || (on->op != "==" && on->op != "=")) throw std::runtime_error(kJoinCondition);
-  JoinScope ls{ast.from_table, left_cols, j.table, right_cols}, rs{ast.from_table, left_cols, j.table, right_cols};
-  try {
-    ls.resolve(on->left.get());
-    rs.resolve(on->right.get());
-  } catch (const std::exception &e) {
-    throw std::runtime_error(std::string("JOIN condition: ") + e.what());
-  }
-  // which tables each side names: {left table, right table}
-  bool key_names[2] = {ls.left, ls.right}, col_names[2] = {rs.left, rs.right};
-  ASTNode *key_side = on->left.get(), *col_side = on->right.get();
-  if (dynamic_cast<VariableNode *>(on->left.get()) && ls.right && !ls.left && !rs.right) {
-    std::swap(key_side, col_side);
-    std::swap(key_names, col_names);
-  }
-  auto *rcol = dynamic_cast<VariableNode *>(col_side);
-  if (!rcol || !col_names[1] || col_names[0] || key_names[1]) throw std::runtime_error(kJoinCondition);
-  p.left_key = key_side->to_cuda_expr();
-  p.right_key = rcol->name.substr(std::string(kJoinRightPrefix).size());
+  lower_on(ast.from_table, left_cols, j, right_cols, p.left_key, p.right_key);
   JoinScope scope{ast.from_table, left_cols, j.table, right_cols};
   for (size_t i = 0; i < ast.select_list.size(); ++i) {
     p.names.push_back(joined_name(ast.select_list[i].get(), i));
@@ -767,6 +787,74 @@ JoinedPlan plan_join(const std::string &left_name, const NameSet &left_cols, con
     }
   }
   return p;
+}
+
+// ------------------------------------------------ query_sql_joined_grouped
+JoinedGroupedPlan plan_sql_joined_grouped(const std::string &sql, const NameSet &left_cols,
+                                          const std::string &right_name, const NameSet &right_cols) {
+  return plan_sql_joined_grouped(sql, left_cols,
+                                 [&](const std::string &name) { return name == right_name ? &right_cols : nullptr; });
+}
+
+JoinedGroupedPlan plan_sql_joined_grouped(const std::string &sql, const NameSet &left_cols,
+                                          const JoinTables &right_cols_of) {
+  std::vector<Token> tokens;
+  JoinedGroupedPlan out;
+  GroupedPlan &p = out.g;
+  try {
+    tokens = tokenize(sql);
+    p.ast = parse_query(tokens);
+  } catch (const std::exception &e) {
+    throw std::runtime_error(std::string("Failed to parse SQL: ") + e.what());
+  }
+  QueryAST &ast = p.ast;
+  if (ast.select_list.empty()) throw std::runtime_error("Empty SELECT list");
+  if (ast.joins.empty())
+    throw std::runtime_error("query_sql_joined_grouped needs a JOIN clause (use query_sql_grouped)");
+  if (ast.joins.size() > 1) throw std::runtime_error("a second JOIN is not supported by query_sql_joined_grouped");
+  if (join_is_left_outer(tokens, 0))
+    throw std::runtime_error("LEFT JOIN under GROUP BY is not supported (an unmatched row needs NULL-aware "
+                             "aggregates)");
+  if (!ast.group_by)
+    throw std::runtime_error("query_sql_joined_grouped needs a GROUP BY clause (use query_sql_joined)");
+  if (ast.group_by->keys.size() != 1) throw std::runtime_error("GROUP BY supports one key expression");
+  if (ast.distinct) throw std::runtime_error("DISTINCT is not supported by query_sql_joined_grouped");
+  for (const auto &e : ast.select_list)
+    if (is_window(e.get())) throw std::runtime_error("window functions are not supported by query_sql_joined_grouped");
+  JoinClause &j = ast.joins[0];
+  const NameSet *right = right_cols_of(j.table);
+  if (!right) throw std::runtime_error("Unknown table: " + j.table + " (attach it first)");
+  const NameSet &right_cols = *right;
+  const size_t m = ast.select_list.size();
+  if (m > WarpDB::kMaxSelectExprs)
+    throw std::runtime_error(kTooManyItems + std::to_string(WarpDB::kMaxSelectExprs) + " expressions");
+  out.right_table = j.table;
+  lower_on(ast.from_table, left_cols, j, right_cols, out.left_key, out.right_key);
+  // every name of every clause to the name the execution layer sees, aggregates' arguments included
+  JoinScope scope{ast.from_table, left_cols, j.table, right_cols};
+  scope.aggs = true;
+  auto resolve = [&](ASTNode *n, const char *clause) {
+    try {
+      scope.resolve(n);
+    } catch (const std::exception &e) {
+      throw std::runtime_error(std::string(clause) + e.what());
+    }
+  };
+  for (size_t i = 0; i < m; ++i) {
+    p.names.push_back(joined_name(ast.select_list[i].get(), i));
+    resolve(ast.select_list[i].get(), "SELECT clause: ");
+  }
+  if (ast.where) resolve(ast.where->get(), "WHERE clause: ");
+  resolve(ast.group_by->keys[0].get(), "GROUP BY clause: ");
+  if (ast.having) resolve(ast.having->get(), "HAVING clause: ");
+  if (ast.order_by) resolve(ast.order_by->expr.get(), "ORDER BY: ");
+  p.cond = lowered_where(ast);
+  p.window = Window(ast);
+  p.key = ast.group_by->keys[0].get();
+  if (is_agg(p.key)) throw std::runtime_error("GROUP BY takes a plain expression, not an aggregate");
+
+  fill_group_slots(p, nullptr);  // the names are resolved already
+  return out;
 }
 
 }  // namespace warpdb

@@ -251,6 +251,25 @@ JoinedPlan plan_join(const std::string &left_name, const NameSet &left_cols, con
                      const NameSet &right_cols, const std::string &left_key, const std::string &right_key,
                      const std::vector<std::string> &exprs, const std::string &where, bool left_outer);
 
+// query_sql_joined_grouped: "SELECT items FROM t [INNER] JOIN u ON c [WHERE w]
+// GROUP BY k [HAVING h] [ORDER BY o [ASC|DESC]] [LIMIT n] [OFFSET m]", each
+// item the key or SUM / AVG / COUNT / MIN / MAX of any expression; every
+// expression, the key and the WHERE are over the columns of both tables.  The
+// ON condition and the names follow plan_sql_joined (qualified or not, u's
+// columns lowered under kJoinRightPrefix), the slots GroupedPlan: `g` is the
+// grouped plan over the resolved tree, so GroupedRun::finish runs on it as it
+// is.  LEFT JOIN is refused: an unmatched row would need NULL-aware aggregates.
+struct JoinedGroupedPlan {
+  std::string right_table;  // u
+  std::string left_key;     // lowered, over t's columns
+  std::string right_key;    // u's column, by its own name
+  GroupedPlan g;
+};
+JoinedGroupedPlan plan_sql_joined_grouped(const std::string &sql, const NameSet &left_cols,
+                                          const JoinTables &right_cols_of);
+JoinedGroupedPlan plan_sql_joined_grouped(const std::string &sql, const NameSet &left_cols,
+                                          const std::string &right_name, const NameSet &right_cols);
+
 // The groups of a GroupedPlan: keys and counts (shared), one set of
 // aggregates per slot.  run.order after finish() as in GroupRun.
 struct GroupedRun {

@@ -255,6 +255,22 @@ PYBIND11_MODULE(pywarpdb, m) {
           "SELECT items FROM t [INNER | LEFT [OUTER]] JOIN u ON <left expression> = <right column> [WHERE c] [LIMIT n] "
           "[OFFSET m]: (names, columns, left row ids, matched right rows).")
       .def(
+          "query_sql_joined_grouped",
+          [](WarpDB &db, const std::string &sql) {
+            warpdb::ResultTable t;
+            {
+              py::gil_scoped_release nogil;
+              t = db.query_sql_joined_grouped(sql);
+            }
+            py::list cols;
+            for (const auto &c : t.columns)
+              cols.append(py::array_t<float>(static_cast<py::ssize_t>(c.size()), c.data()));
+            return py::make_tuple(t.names, cols);
+          },
+          py::arg("sql"),
+          "SELECT key / aggregates FROM t [INNER] JOIN u ON <left expression> = <right column> [WHERE c] GROUP BY key "
+          "[HAVING] [ORDER BY] [LIMIT] [OFFSET] (the probe fused into the grouped pass) -> (names, [float32 arrays]).")
+      .def(
           "query_sql_windowed",
           [](WarpDB &db, const std::string &sql) {
             warpdb::ResultTable t;

@@ -369,12 +369,17 @@ GroupRun run_grouped(const Table &table, const QueryAST &ast, const ASTNode *val
 // through wx_group_agg_multi (every chunk returns the same keys and counts),
 // downloaded, then HAVING and ORDER BY on the host.  WARPDB_GROUP_ROW_ORDER=1:
 // one wx_group_agg call with WX_F_ROW_ORDER per slot instead, so that mode
-// keeps its bit-exact sums.
-warpdb::GroupedRun run_grouped_slots(const Table &table, const warpdb::GroupedPlan &p) {
+// keeps its bit-exact sums.  `joined` (query_sql_joined_grouped) makes a
+// chunk's call instead of wx_group_agg_multi; that route has no row-order mode.
+using GroupChunkCall = std::function<void(const char *const *ex, int32_t k, const char *key, const char *cond,
+                                          wx_launch *L, int64_t cap, int32_t *d_keys, double *const *d_sums,
+                                          int64_t *d_counts, float *const *d_mins, float *const *d_maxs, int64_t *g)>;
+warpdb::GroupedRun run_grouped_slots(const Table &table, const warpdb::GroupedPlan &p,
+                                     const GroupChunkCall *joined = nullptr) {
   const int dev = table.device;
   const int64_t cap = std::max<int64_t>(1, std::min<int64_t>(table.num_rows, 1 << 22));
   const char *ro = std::getenv("WARPDB_GROUP_ROW_ORDER");
-  const bool row_order = ro && std::string(ro) == "1";
+  const bool row_order = !joined && ro && std::string(ro) == "1";
   const std::string key_c = p.key->to_cuda_expr();
   WxTableView v(table);
   wx_launch L = sync_launch(dev);
@@ -432,8 +437,12 @@ warpdb::GroupedRun run_grouped_slots(const Table &table, const warpdb::GroupedPl
           maxs[j] = ptr<float>(dmx[j]);
         }
       }
-      wx_call(wx_group_agg_multi, &v.table, ex, static_cast<int32_t>(k), key_c.c_str(), p.cond.c_str(), &L, 0, cap,
-              ptr<int32_t>(dk), sums, ptr<int64_t>(dc), mins, maxs, nullptr, &g);
+      if (joined)
+        (*joined)(ex, static_cast<int32_t>(k), key_c.c_str(), p.cond.c_str(), &L, cap, ptr<int32_t>(dk), sums,
+                  ptr<int64_t>(dc), mins, maxs, &g);
+      else
+        wx_call(wx_group_agg_multi, &v.table, ex, static_cast<int32_t>(k), key_c.c_str(), p.cond.c_str(), &L, 0, cap,
+                ptr<int32_t>(dk), sums, ptr<int64_t>(dc), mins, maxs, nullptr, &g);
     }
     collect(first, k, g);
   }
@@ -657,10 +666,10 @@ WarpDB::ResultTable WarpDB::query_sql_ordered(const std::string &sql) {
   return out;
 }
 
-WarpDB::ResultTable WarpDB::query_sql_grouped(const std::string &sql) {
-  const warpdb::GroupedPlan p = warpdb::plan_sql_grouped(sql, names_of(table_));
-  const warpdb::GroupedRun r = run_grouped_slots(table_, p);
-  ResultTable out;
+// A grouped run as the result table of its plan: one column per select item
+// over the groups HAVING keeps, in result order, then OFFSET / LIMIT.
+static warpdb::ResultTable grouped_result(const warpdb::GroupedPlan &p, const warpdb::GroupedRun &r) {
+  warpdb::ResultTable out;
   out.names = p.names;
   for (const auto &item : p.items) {
     std::vector<float> col;
@@ -671,6 +680,11 @@ WarpDB::ResultTable WarpDB::query_sql_grouped(const std::string &sql) {
     out.columns.push_back(std::move(col));
   }
   return out;
+}
+
+WarpDB::ResultTable WarpDB::query_sql_grouped(const std::string &sql) {
+  const warpdb::GroupedPlan p = warpdb::plan_sql_grouped(sql, names_of(table_));
+  return grouped_result(p, run_grouped_slots(table_, p));
 }
 
 WarpDB::ResultTable WarpDB::query_sql_windowed(const std::string &sql) {
@@ -796,6 +810,31 @@ WarpDB::ResultTable WarpDB::query_sql_joined(const std::string &sql) {
     return static_cast<const warpdb::NameSet *>(&right_cols);
   });
   return join_run(table_, right.get(), p);
+}
+
+WarpDB::ResultTable WarpDB::query_sql_joined_grouped(const std::string &sql) {
+  std::shared_ptr<const Table> right;
+  warpdb::NameSet right_cols;
+  const warpdb::JoinedGroupedPlan p =
+      warpdb::plan_sql_joined_grouped(sql, names_of(table_), [&](const std::string &name) {
+        right = attached(name);
+        if (!right) return static_cast<const warpdb::NameSet *>(nullptr);
+        right_cols = names_of(*right);
+        return static_cast<const warpdb::NameSet *>(&right_cols);
+      });
+  // the right table under the planner's prefix, as join_run presents it
+  WxTableView lv(table_), rv(*right);
+  for (size_t c = 0; c < rv.names.size(); ++c) rv.names[c] = warpdb::kJoinRightPrefix + rv.names[c];
+  for (size_t c = 0; c < rv.cols.size(); ++c) rv.cols[c].name = rv.names[c].c_str();
+  const std::string rkey = warpdb::kJoinRightPrefix + p.right_key;
+  const GroupChunkCall call = [&](const char *const *ex, int32_t k, const char *key, const char *cond, wx_launch *L,
+                                  int64_t cap, int32_t *d_keys, double *const *d_sums, int64_t *d_counts,
+                                  float *const *d_mins, float *const *d_maxs, int64_t *g) {
+    wx_call(wx_join_group_agg, &lv.table, &rv.table, p.left_key.c_str(), rkey.c_str(),
+            static_cast<int32_t>(WX_JOIN_INNER), ex, k, key, cond, L, 0, cap, d_keys, d_sums, d_counts, d_mins, d_maxs,
+            nullptr, g);
+  };
+  return grouped_result(p.g, run_grouped_slots(table_, p.g, &call));
 }
 
 void WarpDB::query_arrow_sql_windowed(const std::string &sql, ArrowArray *out_array, ArrowSchema *out_schema) {

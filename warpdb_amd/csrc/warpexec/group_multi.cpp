@@ -5,7 +5,6 @@
 
 namespace wx {
 
-namespace {
 int popcount4(int m) { return (m & 1) + ((m >> 1) & 1) + ((m >> 2) & 1) + ((m >> 3) & 1); }
 
 // A plane buffer of at least `bytes`, every byte `fill` when freshly
@@ -16,7 +15,6 @@ void ensure_planes(Workspace &w, hipStream_t s, Buf &b, size_t bytes, int fill) 
   ensure(w, b, bytes, false);
   WX_HIP(hipMemsetAsync(b.p, fill, b.bytes, s));
 }
-}  // namespace
 
 void do_group_multi(const wx_table *t, const char *const *val_exprs, int32_t n_vals, const char *key_expr,
                     const char *cond, const wx_launch *Lp, int32_t key_lo, int64_t capacity, int32_t *d_keys,
@@ -86,10 +84,10 @@ void do_group_multi(const wx_table *t, const char *const *val_exprs, int32_t n_v
       r.hi = it->second.hi;
       ++it->second.uses;
     } else {
-      // (the single-value module is fetched only here and for the device sort
-      // below, where it is needed: a first use compiles it under the
-      // operation lock, which a fetch ahead of every call would avoid at the
-      // price of compiling it for calls that never use it)
+      // (the single-value module is fetched only here, where it is needed: a
+      // first use compiles it under the operation lock, which a fetch ahead of
+      // every call would avoid at the price of compiling it for calls that
+      // never use it)
       const std::shared_ptr<Module> smod = get_module(L.device, single, true);
       r = sample_keys(t, single.cols, smod.get(), w, op.s, op.timed);
       if (r.any) {
@@ -149,7 +147,7 @@ void do_group_multi(const wx_table *t, const char *const *val_exprs, int32_t n_v
     launch(op.mod->fn("wx_group_multi"), grid, &a, op.s, op.timed, (unsigned)gblock);
   }
   // More than WX_GROUP_HSORT_MAX general keys (possible only when the caller
-  // allows that many groups): sorted on the device by wx_group_sum's own
+  // allows that many groups): sorted on the device by the util module's
   // gather + sort, which know the keys only.
   if (capacity > WX_GROUP_HSORT_MAX && t->n_rows > 0) {
     int64_t nh = 0;
@@ -159,15 +157,13 @@ void do_group_multi(const wx_table *t, const char *const *val_exprs, int32_t n_v
       int64_t npad = WX_SORT_LDS;
       while (npad < nh) npad <<= 1;
       ensure(w, w.g_sorted, (size_t)npad * 8, false);
-      const std::shared_ptr<Module> smod =
-          get_module(L.device, group_spec(t, val_exprs[0], key_expr, cond, L, false), true);
       WxGroupGatherArgs ga;
       ga.ctrs = a.ctrs;
       ga.h_used = a.h_used;
       ga.h_tag = a.h_tag;
       ga.keys = static_cast<wx_u64 *>(w.g_sorted.p);
       ga.npad = npad;
-      launch(smod->fn("wx_group_gather"), grid_for(npad, op.d.cus, 8), &ga, op.s);
+      launch(util_module(L.device, true)->fn("wx_group_gather_keys"), grid_for(npad, op.d.cus, 8), &ga, op.s);
       bitonic_u64(L.device, ga.keys, npad, op.s);
       f.sorted = ga.keys;
     }

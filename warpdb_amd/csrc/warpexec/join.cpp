@@ -26,31 +26,8 @@ void read_record(Workspace &w, hipStream_t s) {
 }
 }  // namespace
 
-void do_prepare_join(const wx_table *left, const wx_table *right, const char *left_key_expr, const char *right_key_col,
-                     int32_t join_type, const char *const *exprs, int32_t n_exprs, const char *cond,
-                     const wx_launch *Lp, int32_t with_right_row, int32_t form) {
-  (void)check_join_args(left, right, left_key_expr, right_key_col, join_type, exprs, n_exprs, cond);
-  if (form != WX_JOIN_FORM_DIRECT && form != WX_JOIN_FORM_HASH)
-    fail(WX_ERR_INVALID, "form must be 0 (direct) or 1 (hash)");
-  const wx_launch L = launch_of(Lp);
-  prepare_module(L, join_table_spec());
-  for (const Chunk &k : join_chunks(n_exprs))
-    prepare_module(L, join_spec(left, right, exprs + k.first, k.n, form, join_type == WX_JOIN_LEFT,
-                                with_right_row && k.first == 0, left_key_expr, cond, L));
-}
-
-void do_join_select(const wx_table *left, const wx_table *right, const char *left_key_expr, const char *right_key_col,
-                    int32_t join_type, const char *const *exprs, int32_t n_exprs, const char *cond,
-                    const wx_launch *Lp, float *const *d_out_vals, void *d_out_idx, int32_t idx_bytes,
-                    int64_t row_base, int32_t *d_out_right_row, int64_t *d_count, int64_t *h_count) {
-  const JoinNames names = check_join_args(left, right, left_key_expr, right_key_col, join_type, exprs, n_exprs, cond);
-  const wx_launch L = launch_of(Lp);
-  if (L.flags & WX_F_ROW_ORDER) fail(WX_ERR_UNSUPPORTED, "row-order sums are not available for joins");
-  check_row_ids(left, d_out_idx, idx_bytes, row_base);
-  const int64_t n_right = right->n_rows;
-  const int *d_rkeys = static_cast<const int *>(right->cols[names.right_key].d_ptr);
-
-  Op op(L, join_table_spec());  // held over the phases: the record and the table are the workspace's
+// Phases 1 and 2 of every join call, in the workspace of `op`.
+JoinTable build_join_table(Op &op, const int *d_rkeys, int64_t n_right) {
   Workspace &w = op.w;
   // ---- phase 1: the key range, read with one synchronisation; the span decides the form
   ensure(w, w.jn_rec, WX_JOIN_REC_WORDS * 4, false);
@@ -104,6 +81,43 @@ void do_join_select(const wx_table *left, const wx_table *right, const char *lef
       fail(WX_ERR_UNSUPPORTED,
            "JOIN: the right key is not unique (key " + std::to_string((int32_t)w.jn_host[3]) + ")");
   }
+  JoinTable jt;
+  jt.plan = plan;
+  jt.key_lo = key_lo;
+  jt.span = direct ? (wx_u32)span : 0u;
+  jt.mask = direct ? 0u : (wx_u32)(slots - 1);
+  jt.shift = direct ? 0 : 32 - plan.log2cap;
+  return jt;
+}
+
+void do_prepare_join(const wx_table *left, const wx_table *right, const char *left_key_expr, const char *right_key_col,
+                     int32_t join_type, const char *const *exprs, int32_t n_exprs, const char *cond,
+                     const wx_launch *Lp, int32_t with_right_row, int32_t form) {
+  (void)check_join_args(left, right, left_key_expr, right_key_col, join_type, exprs, n_exprs, cond);
+  if (form != WX_JOIN_FORM_DIRECT && form != WX_JOIN_FORM_HASH)
+    fail(WX_ERR_INVALID, "form must be 0 (direct) or 1 (hash)");
+  const wx_launch L = launch_of(Lp);
+  prepare_module(L, join_table_spec());
+  for (const Chunk &k : join_chunks(n_exprs))
+    prepare_module(L, join_spec(left, right, exprs + k.first, k.n, form, join_type == WX_JOIN_LEFT,
+                                with_right_row && k.first == 0, left_key_expr, cond, L));
+}
+
+void do_join_select(const wx_table *left, const wx_table *right, const char *left_key_expr, const char *right_key_col,
+                    int32_t join_type, const char *const *exprs, int32_t n_exprs, const char *cond,
+                    const wx_launch *Lp, float *const *d_out_vals, void *d_out_idx, int32_t idx_bytes,
+                    int64_t row_base, int32_t *d_out_right_row, int64_t *d_count, int64_t *h_count) {
+  const JoinNames names = check_join_args(left, right, left_key_expr, right_key_col, join_type, exprs, n_exprs, cond);
+  const wx_launch L = launch_of(Lp);
+  if (L.flags & WX_F_ROW_ORDER) fail(WX_ERR_UNSUPPORTED, "row-order sums are not available for joins");
+  check_row_ids(left, d_out_idx, idx_bytes, row_base);
+  const int64_t n_right = right->n_rows;
+  const int *d_rkeys = static_cast<const int *>(right->cols[names.right_key].d_ptr);
+
+  Op op(L, join_table_spec());  // held over the phases: the record and the table are the workspace's
+  Workspace &w = op.w;
+  const JoinTable jt = build_join_table(op, d_rkeys, n_right);  // phases 1 and 2
+  const JoinPlan &plan = jt.plan;
   // ---- phase 3: the probing compactions
   bool first = true;
   for (const Chunk &k : join_chunks(n_exprs)) {
@@ -121,10 +135,10 @@ void do_join_select(const wx_table *left, const wx_table *right, const char *lef
       for (size_t i = 0; i < spec.rcols.size(); ++i) a.rcol[i] = w.jn_slots.p;
     a.rows = static_cast<const int *>(w.jn_rows.p);
     a.slots = static_cast<const wx_u64 *>(w.jn_slots.p);
-    a.key_lo = key_lo;
-    a.span = direct ? (wx_u32)span : 0u;
-    a.mask = direct ? 0u : (wx_u32)(slots - 1);
-    a.shift = direct ? 0 : 32 - plan.log2cap;
+    a.key_lo = jt.key_lo;
+    a.span = jt.span;
+    a.mask = jt.mask;
+    a.shift = jt.shift;
     compact_launch(cop, spec, left, a.c, &a, "wx_join_compact_deep", "wx_join_compact_ticket",
                    first ? d_out_idx : nullptr, idx_bytes, row_base, first ? d_count : nullptr,
                    first ? h_count : nullptr);

@@ -232,6 +232,42 @@ int32_t wx_join_hash_slot(int32_t key, int32_t log2_capacity) {
   return (int32_t)(((uint32_t)key * WX_JOIN_HASH_MUL) >> (32 - log2_capacity));
 }
 
+wx_status wx_join_group_agg(const wx_table *left, const wx_table *right, const char *left_key_expr,
+                            const char *right_key_col, int32_t join_type, const char *const *val_exprs, int32_t n_vals,
+                            const char *group_key_expr, const char *cond, const wx_launch *launch_,
+                            int32_t key_window_lo, int64_t capacity, int32_t *d_keys, double *const *d_sums,
+                            int64_t *d_counts, float *const *d_mins, float *const *d_maxs, int64_t *d_n_groups,
+                            int64_t *h_n_groups, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    do_join_group(left, right, left_key_expr, right_key_col, join_type, val_exprs, n_vals, group_key_expr, cond,
+                  launch_, key_window_lo, capacity, d_keys, d_sums, d_counts, d_mins, d_maxs, d_n_groups, h_n_groups);
+  });
+}
+
+wx_status wx_prepare_join_group(const wx_table *left, const wx_table *right, const char *left_key_expr,
+                                const char *right_key_col, int32_t join_type, const char *const *val_exprs,
+                                int32_t n_vals, uint32_t sum_mask, uint32_t minmax_mask, const char *group_key_expr,
+                                const char *cond, const wx_launch *launch_, int32_t form, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    do_prepare_join_group(left, right, left_key_expr, right_key_col, join_type, val_exprs, n_vals, (int)sum_mask,
+                          (int)minmax_mask, group_key_expr, cond, launch_, form);
+  });
+}
+
+wx_status wx_join_group_geometry(int32_t n_sums, int32_t n_minmax, int32_t form, int32_t *block, int32_t *per_cu,
+                                 int32_t *lds_bytes, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    if (n_sums < 0 || n_sums > WX_GM_MAX || n_minmax < 0 || n_minmax > WX_GM_MAX || n_sums + n_minmax < 1)
+      fail(WX_ERR_INVALID, "n_sums and n_minmax must be between 0 and " + std::to_string(WX_GM_MAX) +
+                               ", and one of them at least 1");
+    if (form != WX_JOIN_FORM_DIRECT && form != WX_JOIN_FORM_HASH)
+      fail(WX_ERR_INVALID, "form must be 0 (direct) or 1 (hash)");
+    if (block) *block = WX_JG_BLOCK(n_sums, n_minmax, form);
+    if (per_cu) *per_cu = WX_JG_PER_CU(n_sums, n_minmax, form);
+    if (lds_bytes) *lds_bytes = WX_JG_LDS_BYTES(n_sums, n_minmax, form);
+  });
+}
+
 wx_status wx_group_partials(const wx_table *table, const char *val_expr, const char *key_expr, const char *cond,
                             const wx_launch *launch_, int32_t key_window_lo, double *d_window, int64_t capacity,
                             int32_t *d_keys, double *d_sums, int64_t *d_counts, int64_t *d_n_extra,

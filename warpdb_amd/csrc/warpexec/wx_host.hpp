@@ -30,6 +30,7 @@
 #include "../kernels/wx_gather_args.h"
 #include "../kernels/wx_radix_args.h"
 #include "../kernels/wx_group_multi_args.h"
+#include "../kernels/wx_join_group_args.h"
 
 namespace wx {
 
@@ -210,6 +211,11 @@ struct Spec {
   std::vector<std::string> join_exprs;
   std::string join_cond;  // the WHERE (`cond` stays empty: see Spec::source)
   std::vector<UsedCol> rcols;
+  // JOIN under GROUP BY (wx_join_group.hip, op WX_OP_JOIN_GROUP): `expr` and
+  // `more` are the values, gm_sums / gm_mms their masks, `key` the left join
+  // key, `cond` the WHERE, gkey the group key; join_form, join_condr and rcols
+  // as for the probe
+  std::string gkey;
   std::string custom;
   std::string extra;  // diagnostic -D list from $WARPDB_EXTRA_DEFINES
 
@@ -275,6 +281,15 @@ JoinNames check_join_args(const wx_table *left, const wx_table *right, const cha
 Spec join_spec(const wx_table *left, const wx_table *right, const char *const *exprs, int32_t n_out, int form,
                bool left_outer, bool right_row, const char *left_key_expr, const char *cond, const wx_launch &L);
 Spec join_table_spec();
+// One launch of the grouped pass over a join: 1 .. WX_GM_MAX values.  The
+// call's checks are check_join_group_args's (n_vals, blank expressions, then
+// check_join_args over the values, the group key and the WHERE, then INNER).
+JoinNames check_join_group_args(const wx_table *left, const wx_table *right, const char *left_key_expr,
+                                const char *right_key_col, int32_t join_type, const char *const *val_exprs,
+                                int32_t n_vals, const char *group_key_expr, const char *cond);
+Spec join_group_spec(const wx_table *left, const wx_table *right, const char *const *val_exprs, int32_t n_vals,
+                     int sum_mask, int mm_mask, int form, const char *left_key_expr, const char *group_key_expr,
+                     const char *cond, const wx_launch &L);
 struct JoinPlan {
   int form = WX_JOIN_FORM_HASH;
   int log2cap = WX_JOIN_MIN_LOG2CAP;  // hash form: log2 of the slots (0 in the direct form)
@@ -380,6 +395,28 @@ void do_join_select(const wx_table *left, const wx_table *right, const char *lef
 void do_prepare_join(const wx_table *left, const wx_table *right, const char *left_key_expr, const char *right_key_col,
                      int32_t join_type, const char *const *exprs, int32_t n_exprs, const char *cond,
                      const wx_launch *Lp, int32_t with_right_row, int32_t form);
+// The right table's key range and its direct or hash table in the workspace
+// of `op` (opened on join_table_spec()): two synchronisations, the second for
+// the duplicate report.  What a probe needs of the result.
+struct JoinTable {
+  JoinPlan plan;
+  int32_t key_lo = 0;
+  wx_u32 span = 0;   // direct form: keys lie in [key_lo, key_lo + span)
+  wx_u32 mask = 0;   // hash form: slots - 1
+  int shift = 0;     // hash form: 32 - log2cap
+};
+JoinTable build_join_table(Op &op, const int *d_rkeys, int64_t n_right);
+
+// join_group.cpp
+void do_join_group(const wx_table *left, const wx_table *right, const char *left_key_expr, const char *right_key_col,
+                   int32_t join_type, const char *const *val_exprs, int32_t n_vals, const char *group_key_expr,
+                   const char *cond, const wx_launch *Lp, int32_t key_lo, int64_t capacity, int32_t *d_keys,
+                   double *const *d_sums, int64_t *d_counts, float *const *d_mins, float *const *d_maxs,
+                   int64_t *d_n_groups, int64_t *h_n_groups);
+void do_prepare_join_group(const wx_table *left, const wx_table *right, const char *left_key_expr,
+                           const char *right_key_col, int32_t join_type, const char *const *val_exprs, int32_t n_vals,
+                           int sum_mask, int mm_mask, const char *group_key_expr, const char *cond,
+                           const wx_launch *Lp, int32_t form);
 
 // group.cpp
 struct KeyRange {
@@ -414,6 +451,8 @@ void do_group_multi(const wx_table *t, const char *const *val_exprs, int32_t n_v
                     const char *cond, const wx_launch *Lp, int32_t key_lo, int64_t capacity, int32_t *d_keys,
                     double *const *d_sums, int64_t *d_counts, float *const *d_mins, float *const *d_maxs,
                     int64_t *d_n_groups, int64_t *h_n_groups);
+int popcount4(int m);
+void ensure_planes(Workspace &w, hipStream_t s, Buf &b, size_t bytes, int fill);
 
 // group_rows.cpp
 void do_group_sum_rows(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond,
