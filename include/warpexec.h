@@ -603,6 +603,39 @@ typedef struct wx_topk_geometry {
 wx_status wx_topk_plan(int64_t n_rows, int32_t k, int32_t cus, const wx_launch *launch, wx_topk_geometry *out,
                        char *err, size_t errlen);
 
+/* The launch geometry of one pass of the range-partitioned GROUP BY (the form
+ * wx_group_sum takes for capacity > 4096 over a key span of 2049 .. 2^24)
+ * over n_rows rows and a span of key_span keys, under the current diagnostic
+ * define list (WX_GP_GRID=<g> caps the tile grid, WX_GP_DIRCH=<w> shortens
+ * the aggregation's directory rounds; WARPDB_EXTRA_DEFINES): the same
+ * arithmetic as the run path's.  cus > 0: a device of that many compute
+ * units (needs no device); cus <= 0: the launch's device.  Tile workgroup g
+ * runs the tiles [g * tiles_per_wg, (g + 1) * tiles_per_wg) of tile_rows rows
+ * each; a work item of the aggregation covers whole workgroups' tiles of one
+ * partition.  A span outside 2049 .. 2^24 is WX_ERR_UNSUPPORTED, a define
+ * out of range (WX_GP_GRID < 1, WX_GP_DIRCH outside 1..4096) WX_ERR_INVALID. */
+typedef struct wx_group_part_geom {
+  int64_t tile_rows;           /* rows of one tile */
+  int64_t n_tiles;             /* tiles of the table */
+  int64_t grid;                /* tile workgroups */
+  int64_t tiles_per_wg;        /* tiles of every workgroup (the last may own fewer) */
+  int64_t n_part;              /* key partitions */
+  int64_t part_keys;           /* keys per partition */
+  int64_t chunk_rows;          /* the floor of the rows one work item aims at */
+  int64_t target_items;        /* work items aimed at over all passing rows */
+  int64_t work_cap;            /* most work items */
+  int64_t dir_chunk;           /* directory words (tiles) an item stages per round */
+  int64_t agg_tiles_per_sweep; /* tiles the waves of an aggregating workgroup take per sweep */
+} wx_group_part_geom;
+wx_status wx_group_part_geometry(int64_t n_rows, int64_t key_span, int32_t cus, const wx_launch *launch,
+                                 wx_group_part_geom *out, char *err, size_t errlen);
+/* Partitioned passes completed so far on the launch's (device, stream): a
+ * plain host counter (no device read, no synchronisation).  The difference
+ * around a wx_group_sum call says which route it took: 0 the LDS window +
+ * global hash, 1 one partitioned pass, 2 a pass re-planned over the exact
+ * range (an aborted pass followed by the window + hash also counts 1). */
+wx_status wx_group_part_passes(const wx_launch *launch, int64_t *passes, char *err, size_t errlen);
+
 /* One shard's ORDER BY .. LIMIT candidates in the exchange layout (520 bytes):
  * wx_topk's d_keys / d_vals / d_idx / d_count pointed at keys, vals, rows and
  * count fill it, so the records of all shards are one all-gather of bytes. */

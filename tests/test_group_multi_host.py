@@ -27,7 +27,7 @@ FROZEN = {
     "wx_args.h": "e0d96028bf0e813ead6aa4a7e75bbae0a4363c761ffa7db9dca58998c4f30785",
     "wx_common.hip": "b852758b8f63c910e29d98da9face7f5156e1e424fa345b459921b0b2ab79779",
     "wx_group.hip": "5a30eb707756263081cba29ec06c96a9857458ff59147523e3926e5b5a5d2c44",
-    "wx_group_part.hip": "692390d8620e35901236ce4515eabfe0bc1b94549112b14c9238b339e745d0b6",
+    "wx_group_part.hip": "2043eb7a0b3f1048913e0ecfc3fe366d901bc5aa127a5b81ae4bf0b623f6fd37",  # + #ifndef WX_GP_DIRCH
     "wx_group_rows.hip": "3809bb618fd8d7714bb9490968143cc9dedc8635bb72971526a345452451f278",
 }
 

@@ -108,6 +108,8 @@ EXPORTED_SYMBOLS = (
     "wx_cast",
     "wx_topk",
     "wx_topk_plan",
+    "wx_group_part_geometry",
+    "wx_group_part_passes",
     "wx_sort_pairs",
     "wx_sort_float",
     "wx_sort_float_from",
@@ -147,6 +149,12 @@ class WxWindowItem(ctypes.Structure):
 class WxTopkGeometry(ctypes.Structure):
     _fields_ = [("grid", ctypes.c_int64), ("span_rows", ctypes.c_int64), ("max_batches", ctypes.c_int64),
                 ("seed_grid", ctypes.c_int64), ("seed_stride_rows", ctypes.c_int64)]
+
+
+class WxGroupPartGeometry(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_int64) for f in (
+        "tile_rows", "n_tiles", "grid", "tiles_per_wg", "n_part", "part_keys", "chunk_rows", "target_items",
+        "work_cap", "dir_chunk", "agg_tiles_per_sweep")]
 
 
 class WxLaunch(ctypes.Structure):
@@ -224,6 +232,8 @@ def load() -> ctypes.CDLL:
         "wx_cast": [P, I32, P, I32, I64, L, E, S],
         "wx_topk": [T, E, E, E, I32, I32, L, I64, P, P, P, P, pI64, E, S],
         "wx_topk_plan": [I64, I32, I32, L, ctypes.POINTER(WxTopkGeometry), E, S],
+        "wx_group_part_geometry": [I64, I64, I32, L, ctypes.POINTER(WxGroupPartGeometry), E, S],
+        "wx_group_part_passes": [L, pI64, E, S],
         "wx_sort_pairs": [P, P, I64, I32, L, E, S],
         "wx_sort_float": [P, I64, I32, L, E, S],
         "wx_sort_float_from": [P, P, I64, I32, L, E, S],
@@ -821,6 +831,31 @@ def topk_plan(n_rows: int, k: int, cus: int = 0, launch: Optional[WxLaunch] = No
     _check(lib.wx_topk_plan(n_rows, k, cus, ctypes.byref(launch) if launch is not None else None, ctypes.byref(out),
                             err, len(err)), err)
     return out
+
+
+def group_part_geometry(n_rows: int, key_span: int, cus: int = 0,
+                        launch: Optional[WxLaunch] = None) -> WxGroupPartGeometry:
+    """The launch geometry of one range-partitioned GROUP BY pass under the
+    current WARPDB_EXTRA_DEFINES (WX_GP_GRID, WX_GP_DIRCH): .tile_rows,
+    .n_tiles, .grid, .tiles_per_wg, .n_part, .part_keys, .chunk_rows,
+    .target_items, .work_cap, .dir_chunk, .agg_tiles_per_sweep.  cus > 0 names
+    the device's compute units (no device needed); otherwise the launch's device."""
+    lib = load()
+    err = _err()
+    out = WxGroupPartGeometry()
+    _check(lib.wx_group_part_geometry(n_rows, key_span, cus, ctypes.byref(launch) if launch is not None else None,
+                                      ctypes.byref(out), err, len(err)), err)
+    return out
+
+
+def group_part_passes(launch: WxLaunch) -> int:
+    """Partitioned GROUP BY passes completed so far on the launch's (device,
+    stream): a host counter, read before and after a call to see its route."""
+    lib = load()
+    err = _err()
+    n = ctypes.c_int64(-1)
+    _check(lib.wx_group_part_passes(ctypes.byref(launch), ctypes.byref(n), err, len(err)), err)
+    return n.value
 
 
 def sort_pairs(d_keys: int, d_vals: int, count: int, ascending: bool, launch: WxLaunch) -> None:

@@ -636,7 +636,12 @@ extern "C" __global__ __launch_bounds__(1024) void wx_group_part_plan(WxGroupPar
 #ifndef WX_GP_AGG_DIAG_NOADD
 #define WX_GP_AGG_DIAG_NOADD 0  // diagnostic: loads without the LDS adds (results invalid)
 #endif
-#define WX_GP_DIRCH 4096  // directory words staged per round
+#ifndef WX_GP_DIRCH
+// directory words staged per round.  A diagnostic build may shrink it (the
+// host refuses a value outside 1..4096 and sizes the LDS for 4096), so that a
+// small table's items take several rounds
+#define WX_GP_DIRCH 4096
+#endif
 extern "C" __global__ __launch_bounds__(WX_GP_BLOCK) void wx_group_part_agg(WxGroupPartArgs a) {
   extern __shared__ wx_u32 wx_s_dyn[];
   const int B = 1 << a.shift;

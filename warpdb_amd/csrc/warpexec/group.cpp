@@ -45,6 +45,44 @@ int64_t gp_max_span() { return (int64_t)WX_GP_STAGE_MAX_PARTS << gp_shift(); }
 // wx_group_sum's workgroup size (512 at two per CU: profiles/r03/abl_group_grid.txt)
 int gp_gblock() { return WX_GBLOCK; }
 
+// The launch geometry of one partitioned pass over n_rows rows and a key
+// span of `span`: the one statement of it (group_partitioned launches it,
+// wx_group_part_geometry reports it).  One 1024-thread tile workgroup per CU
+// (two of 512) up to the 1024 the plan kernel scans, each running
+// tiles_per_wg consecutive tiles.  Two diagnostic defines shrink it so that a
+// small table reaches what only ~1e9 rows reach otherwise: WX_GP_GRID=<g>
+// caps the grid (before tiles_per_wg is derived) and changes nothing else;
+// WX_GP_DIRCH=<w> (1..4096, the kernel's define of the same name) shortens
+// the aggregation's directory rounds, the LDS stays sized for 4096 words.
+GpPlan gp_plan(int64_t n_rows, int64_t span, int cus, const std::string &extra) {
+  if (n_rows < 1) fail(WX_ERR_INVALID, "partitioned GROUP BY: no rows");
+  if (cus < 1) fail(WX_ERR_INVALID, "partitioned GROUP BY: no compute units");
+  if (span <= WX_GROUP_WINDOW || span > gp_max_span())
+    fail(WX_ERR_UNSUPPORTED, "partitioned GROUP BY: key spans of 2049 to 2^24 only");
+  const int grid_cap = define_value(extra, "WX_GP_GRID", INT32_MAX);
+  if (grid_cap < 1) fail(WX_ERR_INVALID, "WX_GP_GRID must be at least 1");
+  GpPlan g;
+  g.dir_chunk = define_value(extra, "WX_GP_DIRCH", WX_GP_AGG_DIR_WORDS);
+  if (g.dir_chunk < 1 || g.dir_chunk > WX_GP_AGG_DIR_WORDS)
+    fail(WX_ERR_INVALID, "WX_GP_DIRCH must be between 1 and 4096");
+  const int agg_r = define_value(extra, "WX_GP_AGG_R", 8);
+  if (agg_r < 1) fail(WX_ERR_INVALID, "WX_GP_AGG_R must be at least 1");
+  g.agg_sweep = WX_GP_BLOCK / 64 * agg_r;
+  g.part_keys = 1ll << gp_shift();
+  g.n_part = (int)((span + g.part_keys - 1) >> gp_shift());
+  g.tile_rows = gp_tile_rows();
+  g.n_tiles = (n_rows + g.tile_rows - 1) / g.tile_rows;
+  g.grid = std::min<int64_t>(std::min<int64_t>((int64_t)cus * (1024 / WX_GP_TBLOCK), 1024), g.n_tiles);
+  g.grid = std::min<int64_t>(g.grid, grid_cap);
+  g.tiles_per_wg = (g.n_tiles + g.grid - 1) / g.grid;
+  g.grid = (g.n_tiles + g.tiles_per_wg - 1) / g.tiles_per_wg;
+  g.chunk_rows = 1 << 16;
+  g.target_items = 4ll * cus;
+  g.work_cap = g.n_part + g.target_items + 2;
+  if (g.work_cap > 4096) fail(WX_ERR_INTERNAL, "partitioned GROUP BY: more than 4096 work items");
+  return g;
+}
+
 // (min, max, passing) over the per-workgroup words mm[4g .. 4g+2]
 KeyRange reduce_mm(const int64_t *h, int64_t groups) {
   KeyRange r;
@@ -110,19 +148,14 @@ struct GpSummary {
 
 GpSummary group_partitioned(const wx_table *t, const std::vector<UsedCol> &cols, Module *mod, DeviceState &d,
                             Workspace &w, hipStream_t s, bool timed, int64_t lo, int64_t span, int64_t capacity,
-                            int32_t *d_keys, double *d_sums, int64_t *d_counts, int64_t *ng) {
+                            int32_t *d_keys, double *d_sums, int64_t *d_counts, int64_t *ng,
+                            const std::string &extra) {
+  const GpPlan plan = gp_plan(t->n_rows, span, d.cus, extra);
   const int shift = gp_shift();
-  const int64_t B = 1ll << shift;
-  const int P = (int)((span + B - 1) >> shift);
-  if (P < 1 || P > WX_GP_STAGE_MAX_PARTS) fail(WX_ERR_INTERNAL, "partitioned GROUP BY: bad partition count");
-  const int64_t tile = gp_tile_rows();
-  const int64_t n_tiles = (t->n_rows + tile - 1) / tile;
-  // one 1024-thread tile workgroup per CU (two of 512); the plan scans G <= 1024
-  int64_t G = std::min<int64_t>(std::min<int64_t>((int64_t)d.cus * (1024 / WX_GP_TBLOCK), 1024), n_tiles);
-  const int64_t tpw = (n_tiles + G - 1) / G;
-  G = (n_tiles + tpw - 1) / tpw;
-  const int64_t target_items = 4ll * d.cus;
-  const int64_t work_cap = P + target_items + 2;
+  const int64_t B = plan.part_keys;
+  const int P = plan.n_part;
+  const int64_t tile = plan.tile_rows, n_tiles = plan.n_tiles, G = plan.grid, tpw = plan.tiles_per_wg;
+  const int64_t target_items = plan.target_items, work_cap = plan.work_cap;
   ensure(w, w.gp_mm, (size_t)G * 32, false);
   ensure(w, w.gp_pcount, (size_t)G * P * 4, false);
   ensure(w, w.gp_ptotal, (size_t)WX_GP_STAGE_MAX_PARTS * 8, false);
@@ -137,7 +170,6 @@ GpSummary group_partitioned(const wx_table *t, const std::vector<UsedCol> &cols,
   ensure(w, w.gp_nwork, 8, false);
   ensure(w, w.gp_pitem, (size_t)(P + 1) * 4, false);
   ensure(w, w.gp_order, (size_t)(work_cap + 8) * 4, false);  // + 8: the XCD-dealt order's empty slots
-  if (work_cap > 4096) fail(WX_ERR_INTERNAL, "partitioned GROUP BY: more than 4096 work items");
   ensure(w, w.gp_psum, (size_t)work_cap * B * 8, false);
   ensure(w, w.gp_pcnt, (size_t)work_cap * B * 4, false);
   ensure(w, w.gp_summary, 32, false);
@@ -163,7 +195,7 @@ GpSummary group_partitioned(const wx_table *t, const std::vector<UsedCol> &cols,
   a.pitem = static_cast<wx_u32 *>(w.gp_pitem.p);
   a.order = static_cast<wx_u32 *>(w.gp_order.p);
   a.work_cap = work_cap;
-  a.chunk = 1 << 16;
+  a.chunk = plan.chunk_rows;
   a.target_items = target_items;
   a.psum = static_cast<double *>(w.gp_psum.p);
   a.pcnt = static_cast<wx_u32 *>(w.gp_pcnt.p);
@@ -221,6 +253,7 @@ GpSummary group_partitioned(const wx_table *t, const std::vector<UsedCol> &cols,
   r.outside = h[1];
   r.mn = h[2];
   r.mx = h[3];
+  ++w.gp_passes;
   return r;
 }
 
@@ -315,12 +348,12 @@ void do_group_sum(const wx_table *t, const char *val_expr, const char *key_expr,
     }
     if (r.any && r.span() > WX_GROUP_WINDOW && r.span() <= gp_max_span()) {
       GpSummary g = group_partitioned(t, spec.cols, op.mod.get(), op.d, op.w, op.s, op.timed, r.lo, r.span(), capacity, d_keys,
-                                      d_sums, d_counts, ng);
+                                      d_sums, d_counts, ng, spec.extra);
       bool done = g.outside == 0;
       if (!done && g.mx - g.mn + 1 > WX_GROUP_WINDOW && g.mx - g.mn + 1 <= gp_max_span()) {
         // some key was outside the planned range: again over the exact one
         g = group_partitioned(t, spec.cols, op.mod.get(), op.d, op.w, op.s, op.timed, g.mn, g.mx - g.mn + 1, capacity, d_keys,
-                              d_sums, d_counts, ng);
+                              d_sums, d_counts, ng, spec.extra);
         if (g.outside) fail(WX_ERR_INTERNAL, "partitioned GROUP BY: rows outside the exact key range");
         done = true;
       }

@@ -376,6 +376,34 @@ wx_status wx_topk_plan(int64_t n_rows, int32_t k, int32_t cus, const wx_launch *
   });
 }
 
+wx_status wx_group_part_geometry(int64_t n_rows, int64_t key_span, int32_t cus, const wx_launch *launch_,
+                                 wx_group_part_geom *out, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    if (!out) fail(WX_ERR_INVALID, "null geometry output");
+    if (cus <= 0) cus = device_state(launch_of(launch_).device, true).cus;
+    const GpPlan P = gp_plan(n_rows, key_span, cus, env_or("WARPDB_EXTRA_DEFINES", ""));
+    out->tile_rows = P.tile_rows;
+    out->n_tiles = P.n_tiles;
+    out->grid = P.grid;
+    out->tiles_per_wg = P.tiles_per_wg;
+    out->n_part = P.n_part;
+    out->part_keys = P.part_keys;
+    out->chunk_rows = P.chunk_rows;
+    out->target_items = P.target_items;
+    out->work_cap = P.work_cap;
+    out->dir_chunk = P.dir_chunk;
+    out->agg_tiles_per_sweep = P.agg_sweep;
+  });
+}
+
+wx_status wx_group_part_passes(const wx_launch *launch_, int64_t *passes, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    if (!passes) fail(WX_ERR_INVALID, "null pass count output");
+    Op op(launch_of(launch_));
+    *passes = op.w.gp_passes;
+  });
+}
+
 wx_status wx_sort_pairs(int32_t *d_keys, float *d_vals, int64_t count, int32_t ascending, const wx_launch *launch_,
                         char *err, size_t errlen) {
   return guarded(err, errlen, [&] { do_sort(d_keys, d_vals, count, 1, ascending, launch_); });

@@ -119,6 +119,7 @@ struct Workspace {
     int uses = 0;
   };
   std::unordered_map<uint64_t, GpMemo> gp_memo;  // last key range per (expressions, columns, rows)
+  int64_t gp_passes = 0;  // completed partitioned passes (wx_group_part_passes: which route a query took)
   Buf cand_k, cand_i, topk_thresh;
   // ORDER BY .. LIMIT heads of any length: keys, SELECT values, local rows,
   // positions and the passing count of one shard; the merge's candidates
@@ -426,6 +427,20 @@ struct KeyRange {
 };
 uint32_t next_pow2(uint64_t v);
 int64_t gp_min_rows();
+struct GpPlan {
+  int64_t tile_rows = 0;     // rows of one tile
+  int64_t n_tiles = 0;       // tiles of the table
+  int64_t grid = 0;          // tile workgroups
+  int64_t tiles_per_wg = 0;  // tiles of every workgroup but (possibly) the last
+  int n_part = 0;            // partitions
+  int64_t part_keys = 0;     // keys per partition
+  int64_t chunk_rows = 0;    // the floor of a work item's rows
+  int64_t target_items = 0;  // work items the plan aims at over all passing rows
+  int64_t work_cap = 0;      // most work items
+  int dir_chunk = 0;         // directory words the aggregation stages per round
+  int agg_sweep = 0;         // tiles all waves of an aggregating workgroup take per sweep
+};
+GpPlan gp_plan(int64_t n_rows, int64_t span, int cus, const std::string &extra);
 void ensure_group_table(Workspace &w, hipStream_t s, uint32_t hcap);
 KeyRange sample_keys(const wx_table *t, const std::vector<UsedCol> &cols, Module *mod, Workspace &w, hipStream_t s,
                      bool timed);
