@@ -157,6 +157,23 @@ wx_status wx_prepare_multi(const wx_table *table, const char *const *exprs, int3
  * outputs grow; the diagnostic define list may override it); 0 when n_exprs
  * is out of range or the geometry is invalid. */
 int32_t wx_select_tile_rows(int32_t n_exprs);
+/* What the last ordered compaction on the launch's (device, stream) launched
+ * -- wx_project_filter in WX_MODE_COMPACT, wx_project_filter_multi, a
+ * broadcast launch of wx_window_select, a probe launch of wx_join_select:
+ * plain host numbers (no device read, no synchronisation).  All zero before
+ * any such launch and after a call over an empty table.  The pipelined
+ * kernel runs min(n_tiles, resident workgroups) workgroups that take tiles
+ * from a ticket counter; the diagnostic variable WARPDB_COMPACT_GRID=<n>
+ * (an integer >= 1, else WX_ERR_INVALID from the compacting call) caps that
+ * grid, so that few workgroups run many tiles each.  The one-tile-per-
+ * workgroup schedule (WARPDB_COMPACT_SCHED=ticket) ignores the cap. */
+typedef struct wx_compact_geom {
+  int64_t tile_rows; /* rows of one tile */
+  int64_t n_tiles;   /* tiles of the table */
+  int64_t grid;      /* workgroups launched (n_tiles under the ticket schedule) */
+  int64_t deep;      /* 1: the pipelined kernel, 0: one tile per workgroup */
+} wx_compact_geom;
+wx_status wx_compact_last_launch(const wx_launch *launch, wx_compact_geom *out, char *err, size_t errlen);
 
 /* Row gather with several outputs (late materialisation): n_exprs
  * expressions (1 .. WX_MAX_OUTPUTS) at a list of row ids.  For k < count,

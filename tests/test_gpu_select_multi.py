@@ -138,14 +138,23 @@ def test_null_outputs(m, null):
 
 @pytest.mark.parametrize("m", [2, 4])
 def test_tiny_tiles_pipeline_and_lookback_window(m, monkeypatch):
-    # 512-row tiles: ~1950 tiles, so every workgroup pipelines several tiles
-    # and the look-back window moves past 64 predecessors
+    # 512-row tiles: 1954 tiles, and the look-back window moves past 64
+    # predecessors.  The grid is min(tiles, resident workgroups) -- measured
+    # on the 256 CUs of an MI355X: 1536 workgroups for m = 2, 1280 for m = 4
+    # -- so grid * 3 > n_tiles: the workgroups that start first take two
+    # tiles at entry (a further one only while later workgroups have not
+    # started), so about ceil(n_tiles / grid) + 1 = 3 tiles at the most, and
+    # the late ones find the tickets gone.  The pipeline's steady state
+    # (three tiles in flight in one workgroup, iteration after iteration) is
+    # not what this test reaches; tests/test_gpu_compact_edges.py runs it.
     monkeypatch.setenv("WARPDB_EXTRA_DEFINES", "WX_COMPACT_GROUPS=1,WX_COMPACT_DWAVES=2")
     assert wx.select_tile_rows(m) == 512
     table, _ = device_table(BIG, 0)
     ref_vals, ref_idx = reference(BIG, "gt15")
     cnt, vals, idx = run(table, lowered(EXPRS[:m]), lower_cond(CONDS["gt15"]), ids=4)
     check(cnt, vals, idx, ref_vals, ref_idx)
+    g = wx.compact_last_launch(launch())
+    assert (g.deep, g.tile_rows, g.n_tiles) == (1, 512, -(-BIG // 512)) and 64 < g.grid <= g.n_tiles
 
 
 def test_ticket_schedule_matches_default(monkeypatch):

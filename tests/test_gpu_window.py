@@ -278,14 +278,23 @@ def test_ticket_schedule_matches_default_over_chunks(monkeypatch):
 
 @pytest.mark.parametrize("keyset", ["dense2048", "span2049"])
 def test_tiny_tiles_pipeline_and_lookback_window(keyset, monkeypatch):
-    # 512-row tiles: ~600 tiles, so every workgroup pipelines several tiles and
-    # the look-back window moves past 64 predecessors
+    # 512-row tiles: 541 (dense form) / 601 (search form) tiles, and the
+    # look-back window moves past 64 predecessors.  That is fewer tiles than
+    # an MI355X keeps workgroups resident, so the grid is n_tiles (measured:
+    # 541 / 601): the workgroups that start first take two tiles at entry (a
+    # further one only while later workgroups have not started), so about
+    # ceil(n_tiles / grid) + 1 = 2 tiles at the most, and the rest find the
+    # tickets gone.  The pipeline's steady state (three tiles in flight in one
+    # workgroup, iteration after iteration) is not what this test reaches;
+    # tests/test_gpu_compact_edges.py runs it.
     search = not KEYSETS[keyset][1]
     n = sizes(search)[6]
     monkeypatch.setenv("WARPDB_EXTRA_DEFINES", "WX_COMPACT_GROUPS=1,WX_COMPACT_DWAVES=2")
     assert wx.window_tile_rows(2, 1, search) == 512
     table, _ = device_table(n, keyset, "most")
     check(run(table, PLAIN1, ITEM1, ids=4), expected(columns(n, keyset, "most"), PLAIN1, ITEM1))
+    g = wx.compact_last_launch(launch())
+    assert (g.deep, g.tile_rows, g.n_tiles) == (1, 512, -(-n // 512)) and 64 < g.grid <= g.n_tiles
 
 
 @pytest.mark.parametrize("ids,row_base", [(0, 0), (4, 1000), (8, 1 << 33)])

@@ -76,6 +76,7 @@ EXPORTED_SYMBOLS = (
     "wx_project_filter_multi",
     "wx_prepare_multi",
     "wx_select_tile_rows",
+    "wx_compact_last_launch",
     "wx_gather_multi",
     "wx_prepare_gather",
     "wx_gather_tile_rows",
@@ -157,6 +158,10 @@ class WxGroupPartGeometry(ctypes.Structure):
         "work_cap", "dir_chunk", "agg_tiles_per_sweep")]
 
 
+class WxCompactGeometry(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_int64) for f in ("tile_rows", "n_tiles", "grid", "deep")]
+
+
 class WxLaunch(ctypes.Structure):
     _fields_ = [
         ("device", ctypes.c_int32),
@@ -234,6 +239,7 @@ def load() -> ctypes.CDLL:
         "wx_topk_plan": [I64, I32, I32, L, ctypes.POINTER(WxTopkGeometry), E, S],
         "wx_group_part_geometry": [I64, I64, I32, L, ctypes.POINTER(WxGroupPartGeometry), E, S],
         "wx_group_part_passes": [L, pI64, E, S],
+        "wx_compact_last_launch": [L, ctypes.POINTER(WxCompactGeometry), E, S],
         "wx_sort_pairs": [P, P, I64, I32, L, E, S],
         "wx_sort_float": [P, I64, I32, L, E, S],
         "wx_sort_float_from": [P, P, I64, I32, L, E, S],
@@ -380,6 +386,17 @@ def prepare_multi(table: Table, exprs: Sequence[str], cond: Optional[str] = None
 def select_tile_rows(n_exprs: int) -> int:
     """Rows per compaction tile of an n_exprs-output call (0: out of range)."""
     return int(load().wx_select_tile_rows(n_exprs))
+
+
+def compact_last_launch(launch: WxLaunch) -> WxCompactGeometry:
+    """What the last ordered compaction on the launch's (device, stream)
+    launched: .tile_rows, .n_tiles, .grid, .deep (1: the pipelined kernel).
+    Host numbers; all zero before any launch and after an empty table."""
+    lib = load()
+    err = _err()
+    out = WxCompactGeometry()
+    _check(lib.wx_compact_last_launch(ctypes.byref(launch), ctypes.byref(out), err, len(err)), err)
+    return out
 
 
 def gather_multi(table: Table, exprs: Sequence[str], d_rows: int, idx_bytes: int, count: int, launch: WxLaunch,

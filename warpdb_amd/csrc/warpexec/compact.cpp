@@ -39,9 +39,13 @@ void compact_launch(Op &op, const Spec &spec, const wx_table *t, WxCompactArgs &
                     const char *ticket_fn, void *d_out_idx, int32_t idx_bytes, int64_t row_base, int64_t *d_count,
                     int64_t *h_count) {
   Workspace &w = op.w;
+  // (read before anything is enqueued: a bad $WARPDB_COMPACT_GRID leaves the workspace as it was)
+  const bool ticket = compact_ticket_sched();
+  const int64_t grid_cap = ticket ? 0 : compact_grid_cap();
   int64_t *count_dst = count_slot(w, w.count_tmp, d_count, h_count != nullptr);
   const int64_t tile_rows = (int64_t)spec.dwaves * 64 * 4 * spec.groups;
   const int64_t n_tiles = (t->n_rows + tile_rows - 1) / tile_rows;
+  w.cs_last = {0, 0, 0, 0};
   if (n_tiles == 0) {
     if (count_dst) WX_HIP(hipMemsetAsync(count_dst, 0, 8, op.s));
   } else {
@@ -68,11 +72,13 @@ void compact_launch(Op &op, const Spec &spec, const wx_table *t, WxCompactArgs &
     c.diag = nullptr;
     // diagnostics only, and only the single-output kernel records them
     const bool timeline = spec.more.empty() && spec.extra.find("WX_DIAG_TIMELINE") != std::string::npos;
-    if (!compact_ticket_sched()) {
+    if (!ticket) {
       // Persistent pipelined kernel, tiles from a ticket counter: any grid
       // size is correct (a workgroup that starts late finds the tickets
       // taken and exits); one workgroup per CU at the occupancy the
       // kernel's LDS allows is what keeps every CU streaming.
+      // $WARPDB_COMPACT_GRID caps the grid (diagnostic: fewer workgroups,
+      // all resident, each running more tiles).
       hipFunction_t fn = op.mod->fn(deep_fn);
       int per_cu = 0, lds = 0;
       const unsigned cblock = (unsigned)(spec.dwaves + 1) * 64;
@@ -80,7 +86,10 @@ void compact_launch(Op &op, const Spec &spec, const wx_table *t, WxCompactArgs &
       WX_HIP(hipFuncGetAttribute(&lds, HIP_FUNC_ATTRIBUTE_SHARED_SIZE_BYTES, fn));
       const int lds_limit = lds > 0 ? (160 * 1024) / lds : 64;
       const int bpc = std::max(1, std::min(per_cu, lds_limit));
-      const unsigned grid = (unsigned)std::min<int64_t>(n_tiles, (int64_t)op.d.cus * bpc);
+      int64_t full = std::min<int64_t>(n_tiles, (int64_t)op.d.cus * bpc);
+      if (grid_cap) full = std::min(full, grid_cap);
+      const unsigned grid = (unsigned)full;
+      w.cs_last = {tile_rows, n_tiles, (int64_t)grid, 1};
       if (std::getenv("WARPDB_DEBUG"))
         std::fprintf(stderr, "[warpexec] %s: occupancy %d/CU, lds %d B, lds_limit %d, bpc %d, grid %u, tiles %lld\n",
                      deep_fn, per_cu, lds, lds_limit, bpc, grid, (long long)n_tiles);
@@ -92,6 +101,7 @@ void compact_launch(Op &op, const Spec &spec, const wx_table *t, WxCompactArgs &
       launch(fn, grid, args, op.s, op.timed, cblock);
       if (timeline) print_timeline(op, grid, n_tiles);
     } else {
+      w.cs_last = {tile_rows, n_tiles, n_tiles, 0};
       launch(op.mod->fn(ticket_fn), (unsigned)n_tiles, args, op.s, op.timed, (unsigned)spec.dwaves * 64);
     }
   }

@@ -82,6 +82,14 @@ Workspace &workspace(int dev, hipStream_t s) {
   return ref;
 }
 
+// The workspace of (dev, s) if an operation has opened one, else null: no
+// device call, so a report of host-side state works where no device is.
+Workspace *find_workspace(int dev, hipStream_t s) {
+  Lock lk(g_mu);
+  auto it = g_ws.find(std::make_pair(dev, s));
+  return it == g_ws.end() ? nullptr : it->second.get();
+}
+
 uint64_t fnv1a(const std::string &s) {
   uint64_t h = 1469598103934665603ull;
   for (unsigned char c : s) {

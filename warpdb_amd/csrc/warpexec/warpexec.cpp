@@ -58,6 +58,19 @@ int32_t wx_select_tile_rows(int32_t n_exprs) {
   }
 }
 
+wx_status wx_compact_last_launch(const wx_launch *launch_, wx_compact_geom *out, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    if (!out) fail(WX_ERR_INVALID, "null geometry output");
+    const wx_launch L = launch_of(launch_);
+    *out = {0, 0, 0, 0};
+    // (no workspace yet: nothing was launched there, and none is made for the question)
+    if (Workspace *w = find_workspace(L.device, static_cast<hipStream_t>(L.stream))) {
+      OpLock lock(w->op_mu);
+      *out = w->cs_last;
+    }
+  });
+}
+
 wx_status wx_gather_multi(const wx_table *table, const char *const *exprs, int32_t n_exprs, const void *d_rows,
                           int32_t idx_bytes, int64_t row_base, int64_t count, const int64_t *d_count,
                           const wx_launch *launch_, float *const *d_out_vals, int64_t *d_out_rows, int64_t out_row_base,

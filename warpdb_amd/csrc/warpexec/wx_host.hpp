@@ -87,6 +87,7 @@ struct Workspace {
   Buf ctrs;        // u64[8]: [0] ticket, [1] error bits, [2] retired workgroups (compaction)
   Buf status;      // u64[n_tiles + 1] compaction look-back words {epoch | flag | value}
   uint32_t cs_epoch = 0;  // epoch of the last compaction launch (0: words all zero)
+  wx_compact_geom cs_last = {0, 0, 0, 0};  // what the last compaction launched (wx_compact_last_launch)
   uint64_t host_word = 0;  // landing slot of small synchronous D2H reads (outlives the copy)
   uint64_t *h_err = nullptr;  // pinned: the error words of ctrs / g_ctrs, read with one stream sync
   bool topk_clean = false;    // topk_thresh is zero (see do_topk)
@@ -232,6 +233,7 @@ std::string one_line(const char *s);
 int define_value(const std::string &extra, const std::string &name, int dflt);
 void compact_geometry(Spec &spec);
 bool compact_ticket_sched();
+int64_t compact_grid_cap();
 void select_geometry(Spec &spec, int nout);
 void window_geometry(Spec &spec, int nout, int n_items, bool search);
 void join_geometry(Spec &spec, int nout, int form, bool right_row);
@@ -303,6 +305,7 @@ uint64_t fnv1a(const std::string &s);
 void ensure(Workspace &w, Buf &b, size_t bytes, bool zero);
 DeviceState &device_state(int dev, bool need_device);
 Workspace &workspace(int dev, hipStream_t s);
+Workspace *find_workspace(int dev, hipStream_t s);
 std::shared_ptr<Module> get_module(int dev, const Spec &spec, bool load);
 void prepare_module(const wx_launch &L, const Spec &spec);
 bool device_visible(const wx_launch &L);
