@@ -8,6 +8,7 @@ from __future__ import annotations
 
 import hashlib
 import os
+import re
 import subprocess
 
 import pytest
@@ -68,6 +69,36 @@ def test_single_value_spec_keys_and_programs_unchanged():
         assert st == 0, err.value
         text = src.value.decode()
         assert "wx_group_sum" in text and "wx_group_multi" not in text and "WX_GM_" not in text
+
+
+def program_text(*args):
+    """The program text of a module the C ABI does not hand out (tests/cpp/program_text.cpp: the code generator, no device)."""
+    r = subprocess.run(["make", "-s", "-C", os.path.join(ROOT, "tests", "cpp"), "bin/program_text"],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    r = subprocess.run([os.path.join(ROOT, "tests", "cpp", "bin", "program_text"), *map(str, args)],
+                       capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    return r.stdout
+
+
+def test_program_text_has_one_body(monkeypatch):
+    """A multi-value or grouped-join module takes the window body and the block helpers from the shared sources,
+    once each and ahead of the kernels; a single-value GROUP program holds neither."""
+    monkeypatch.delenv("WARPDB_EXTRA_DEFINES", raising=False)
+    for args in (("group_multi", 2, 0b01, 0b10), ("join_group", 1, 0b1, 0, "direct"),
+                 ("join_group", 4, 0b0011, 0b1110, "hash", "left")):
+        text = program_text(*args)
+        kernels = text.index('#line 1 "wx_group_multi.hip"')
+        for shared in ('#line 1 "wx_group_window.hip"', '#line 1 "wx_block.hip"'):
+            assert text.count(shared) == 1 and text.index(shared) < kernels, args
+        assert text.index('#line 1 "wx_block.hip"') < text.index('#line 1 "wx_group_window.hip"')
+        assert text.count('#line 1 "wx_group_multi.hip"') == 1
+        assert len(re.findall(r"\bvoid wx_group_multi_finalize\(", text)) == 1
+        assert ('#line 1 "wx_join_group.hip"' in text) == (args[0] == "join_group")
+    single = wx.prepare(table(price="f32", quantity="i32"), wx.OP_GROUP, "price[idx]", None, "quantity[idx]", 0,
+                        launch=no_custom(), want_source=True)
+    assert "wx_group_sum" in single and "wx_group_window.hip" not in single and "wx_block.hip" not in single
 
 
 def test_header_parses_as_c11(tmp_path):

@@ -27,9 +27,7 @@
 // value planes are this family's: plane p of the summed values is the p-th
 // set bit of the sum mask, likewise for MIN / MAX.  Idle values (restored by
 // wx_group_multi_finalize): sums and counts 0, tags 0, minima ~0, maxima 0.
-struct WxGroupMultiArgs {
-  const void *col[WX_MAX_COLS];
-  wx_i64 n_rows;
+struct WxGroupPlanes {
   wx_u64 *win_cnt;  // [WX_GROUP_WINDOW]
   double *win_sum;  // [s][WX_GROUP_WINDOW]
   wx_u32 *win_min;  // [q][WX_GROUP_WINDOW] order-mapped, ~0 = none
@@ -42,23 +40,17 @@ struct WxGroupMultiArgs {
   wx_u32 *h_max;    // [q][hcap]
   wx_u64 *ctrs;     // [0] used slots, [1] error bits
   wx_u32 hmask;     // hcap - 1 (hcap a power of two)
-  int key_lo;
+  int key_lo;       // the window's first key
+};
+
+struct WxGroupMultiArgs {
+  const void *col[WX_MAX_COLS];
+  wx_i64 n_rows;
+  WxGroupPlanes acc;
 };
 
 struct WxGroupMultiFinArgs {
-  wx_u64 *win_cnt;
-  double *win_sum;
-  wx_u32 *win_min;
-  wx_u32 *win_max;
-  wx_u64 *h_tag;
-  wx_u64 *h_cnt;
-  wx_u32 *h_used;
-  double *h_sum;
-  wx_u32 *h_min;
-  wx_u32 *h_max;
-  wx_u64 *ctrs;
-  wx_u32 hmask;
-  int key_lo;
+  WxGroupPlanes acc;
   const wx_u64 *sorted;  // nullable: general-key entries pre-sorted on the device (> WX_GROUP_HSORT_MAX)
   int *out_keys;
   wx_i64 *out_counts;

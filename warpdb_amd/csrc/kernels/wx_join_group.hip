@@ -2,8 +2,8 @@
 // every row is looked up in the right table's direct or hash table and the
 // kept rows are added into wx_group_multi's LDS window + general-key hash, so
 // nothing is written per row.  Concatenated after wx_common.hip,
-// wx_group_multi.hip (the accumulator layout, wx_gm_hash_add and
-// wx_group_multi_finalize), wx_join.hip (the lookup and the right-column
+// wx_group_window.hip (the accumulator layout, wx_gm_hash_add and
+// wx_group_multi_finalize), wx_group_multi.hip (WX_UNROLL), wx_join.hip (the lookup and the right-column
 // binding) and wx_join_group_args.h.
 #if WX_OP == WX_OP_JOIN_GROUP
 // The prelude defines, beside wx_group_multi's (WX_NOUT 1 .. 4, WX_EXPR ..
@@ -92,7 +92,7 @@ extern "C" __global__ __launch_bounds__(WX_JG_BLOCK(wxgm::NS, wxgm::NQ, WX_JOIN_
   // dimension attribute of a few values puts many lanes of a wave on one bin.
   // Sum-only builds; full waves only.
   if ((wx_u == 0 && wx_e == 0) || wx_lead_on) {
-    const wx_u32 wx_lb = wx_pass ? (wx_u32)(wx_gk - wx_a.key_lo) : 0xffffffffu;
+    const wx_u32 wx_lb = wx_pass ? (wx_u32)(wx_gk - wx_a.acc.key_lo) : 0xffffffffu;
     const wx_u32 wx_b0 = (wx_u32)__builtin_amdgcn_readfirstlane((int)wx_lb);
     const wx_u64 wx_m = __builtin_amdgcn_ballot_w64(wx_lb == wx_b0 && wx_b0 < (wx_u32)WX_GWIN);
     const bool wx_shared = __builtin_popcountll(wx_m) >= WX_GROUP_LEAD;
@@ -111,7 +111,7 @@ extern "C" __global__ __launch_bounds__(WX_JG_BLOCK(wxgm::NS, wxgm::NQ, WX_JOIN_
   }
 #endif
   if (wx_pass) {
-    const wx_u32 wx_bin = (wx_u32)(wx_gk - wx_a.key_lo);
+    const wx_u32 wx_bin = (wx_u32)(wx_gk - wx_a.acc.key_lo);
     if (wx_bin < (wx_u32)WX_GWIN) {
       atomicAdd(&wx_s_cnt[wx_bin], 1u);
 #pragma unroll
@@ -126,7 +126,7 @@ extern "C" __global__ __launch_bounds__(WX_JG_BLOCK(wxgm::NS, wxgm::NQ, WX_JOIN_
         }
       }
     } else {
-      wx_gm_hash_add(wx_a, wx_gk, wx_v);
+      wx_gm_hash_add(wx_a.acc, wx_gk, wx_v);
     }
   }
   WX_STRIDE_LOOP_END
@@ -136,14 +136,14 @@ extern "C" __global__ __launch_bounds__(WX_JG_BLOCK(wxgm::NS, wxgm::NQ, WX_JOIN_
   for (int i = threadIdx.x; i < WX_GWIN; i += wxjg::BLOCK) {
     const wx_u32 c = wx_s_cnt[i];
     if (c) {
-      atomicAdd(&wx_a.win_cnt[i], (wx_u64)c);
+      atomicAdd(&wx_a.acc.win_cnt[i], (wx_u64)c);
 #pragma unroll
-      for (int p = 0; p < wxgm::NS; ++p) atomicAdd(&wx_a.win_sum[p * WX_GWIN + i], wx_s_sum[p * WX_GWIN + i]);
+      for (int p = 0; p < wxgm::NS; ++p) atomicAdd(&wx_a.acc.win_sum[p * WX_GWIN + i], wx_s_sum[p * WX_GWIN + i]);
 #pragma unroll
       for (int p = 0; p < wxgm::NQ; ++p)
         if (wx_s_max[p * WX_GWIN + i] != 0u) {
-          atomicMin(&wx_a.win_min[p * WX_GWIN + i], wx_s_min[p * WX_GWIN + i]);
-          atomicMax(&wx_a.win_max[p * WX_GWIN + i], wx_s_max[p * WX_GWIN + i]);
+          atomicMin(&wx_a.acc.win_min[p * WX_GWIN + i], wx_s_min[p * WX_GWIN + i]);
+          atomicMax(&wx_a.acc.win_max[p * WX_GWIN + i], wx_s_max[p * WX_GWIN + i]);
         }
     }
   }

@@ -177,18 +177,7 @@ extern "C" __global__ __launch_bounds__(WX_GCOMB_BLOCK) void wx_group_combine_sl
     s_ent[i] = e;
   }
   __syncthreads();
-  for (int k = 2; k <= npad; k <<= 1)
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      for (int i = tid; i < npad; i += WX_GCOMB_BLOCK) {
-        const int p = i ^ j;
-        if (p > i) {
-          const wx_u64 x = s_ent[i], y = s_ent[p];
-          const bool up = (i & k) == 0;
-          if ((x > y) == up) { s_ent[i] = y; s_ent[p] = x; }
-        }
-      }
-      __syncthreads();
-    }
+  WX_BITONIC_LDS(s_ent, npad, tid, WX_GCOMB_BLOCK, true)
   // unique keys: run heads ranked by a block scan (4 consecutive entries per thread)
   constexpr int PER = WX_GROUP_SLOT_MAX / WX_GCOMB_BLOCK;
   wx_u32 hm = 0u, nh = 0u;

@@ -401,7 +401,6 @@ void do_group_sum(const wx_table *t, const char *val_expr, const char *key_expr,
   // sort (fusing it into wx_group_sum's last workgroup measured slower,
   // DESIGN.md 5.2).
   WxGroupFinArgs f;
-  f.sorted = nullptr;
   f.win_sum = a.win_sum;
   f.win_cnt = a.win_cnt;
   f.h_tag = a.h_tag;
@@ -431,36 +430,8 @@ void do_group_sum(const wx_table *t, const char *val_expr, const char *key_expr,
     const unsigned grid = grid_for(((t->n_rows + 3) / 4 + gblock / WX_BLOCK - 1) / (gblock / WX_BLOCK), op.d.cus, gpc);
     launch(op.mod->fn("wx_group_sum"), grid, &a, op.s, op.timed, (unsigned)gblock);
   }
-  // More than WX_GROUP_HSORT_MAX general keys (possible only when the caller
-  // allows that many groups): sort them on the device for the finalize.
-  const wx_u64 *sorted = nullptr;
-  if (capacity > WX_GROUP_HSORT_MAX && t->n_rows > 0) {
-    int64_t nh = 0;
-    WX_HIP(hipMemcpyAsync(&nh, a.ctrs, 8, hipMemcpyDeviceToHost, op.s));
-    WX_HIP(hipStreamSynchronize(op.s));
-    if (nh > WX_GROUP_HSORT_MAX) {
-      int64_t npad = WX_SORT_LDS;
-      while (npad < nh) npad <<= 1;
-      ensure(op.w, op.w.g_sorted, (size_t)npad * 8, false);
-      WxGroupGatherArgs ga;
-      ga.ctrs = a.ctrs;
-      ga.h_used = a.h_used;
-      ga.h_tag = a.h_tag;
-      ga.keys = static_cast<wx_u64 *>(op.w.g_sorted.p);
-      ga.npad = npad;
-      launch(op.mod->fn("wx_group_gather"), grid_for(npad, op.d.cus, 8), &ga, op.s);
-      bitonic_u64(L.device, ga.keys, npad, op.s);
-      sorted = ga.keys;
-    }
-  }
-  f.sorted = sorted;
-  void *params[] = {&f};
-  WX_HIP(hipModuleLaunchKernel(op.mod->fn("wx_group_finalize"), 1, 1, 1, 1024, 1, 1, 0, op.s, params, nullptr));  // WX_GFIN_BLOCK
-  if (h_n_groups) {  // read before the error check: a capacity error still reports the count
-    WX_HIP(hipStreamSynchronize(op.s));
-    WX_HIP(hipMemcpy(h_n_groups, ng, 8, hipMemcpyDeviceToHost));
-  }
-  if ((L.flags & WX_F_SYNC) || h_n_groups) check_errors(op.w);
+  f.sorted = sort_general_keys(op, op.mod.get(), a.ctrs, a.h_used, a.h_tag, capacity, t->n_rows > 0);
+  finish_group(op, op.mod->fn("wx_group_finalize"), &f, ng, h_n_groups);
 }
 
 void do_group_combine(const double *d_window, int32_t key_lo, const int32_t *xk, const double *xs, const int64_t *xc,

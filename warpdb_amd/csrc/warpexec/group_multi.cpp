@@ -5,17 +5,6 @@
 
 namespace wx {
 
-int popcount4(int m) { return (m & 1) + ((m >> 1) & 1) + ((m >> 2) & 1) + ((m >> 3) & 1); }
-
-// A plane buffer of at least `bytes`, every byte `fill` when freshly
-// allocated: the finalize leaves the planes idle, so an old one is as it
-// should be.
-void ensure_planes(Workspace &w, hipStream_t s, Buf &b, size_t bytes, int fill) {
-  if (b.p && b.bytes >= bytes) return;
-  ensure(w, b, bytes, false);
-  WX_HIP(hipMemsetAsync(b.p, fill, b.bytes, s));
-}
-
 void do_group_multi(const wx_table *t, const char *const *val_exprs, int32_t n_vals, const char *key_expr,
                     const char *cond, const wx_launch *Lp, int32_t key_lo, int64_t capacity, int32_t *d_keys,
                     double *const *d_sums, int64_t *d_counts, float *const *d_mins, float *const *d_maxs,
@@ -52,20 +41,6 @@ void do_group_multi(const wx_table *t, const char *const *val_exprs, int32_t n_v
   const int gblock = WX_GM_BLOCK(ns, nq);
   Op op(L, spec);
   Workspace &w = op.w;
-  ensure_group_table(w, op.s, next_pow2(std::max<int64_t>(4096, 2 * capacity)));
-  const size_t hcap = w.g_hcap;
-  ensure(w, w.g_win_cnt, WX_GROUP_WINDOW * 8, true);
-  ensure(w, w.g_ctrs, 64, true);
-  if (ns) {
-    ensure_planes(w, op.s, w.gm_win_sum, (size_t)ns * WX_GROUP_WINDOW * 8, 0);
-    ensure_planes(w, op.s, w.gm_sum, (size_t)ns * hcap * 8, 0);
-  }
-  if (nq) {
-    ensure_planes(w, op.s, w.gm_win_min, (size_t)nq * WX_GROUP_WINDOW * 4, 0xff);
-    ensure_planes(w, op.s, w.gm_win_max, (size_t)nq * WX_GROUP_WINDOW * 4, 0);
-    ensure_planes(w, op.s, w.gm_min, (size_t)nq * hcap * 4, 0xff);
-    ensure_planes(w, op.s, w.gm_max, (size_t)nq * hcap * 4, 0);
-  }
   int64_t *ng = count_slot(w, w.g_ngroups, d_n_groups);
   // A caller expecting many groups on a large table: the key range of the
   // single-value call over the first value (its memo, else its 65 536-row
@@ -104,33 +79,9 @@ void do_group_multi(const wx_table *t, const char *const *val_exprs, int32_t n_v
   WxGroupMultiArgs a;
   fill_cols(t, spec.cols, a.col);
   a.n_rows = t->n_rows;
-  a.win_cnt = static_cast<wx_u64 *>(w.g_win_cnt.p);
-  a.win_sum = static_cast<double *>(w.gm_win_sum.p);
-  a.win_min = static_cast<wx_u32 *>(w.gm_win_min.p);
-  a.win_max = static_cast<wx_u32 *>(w.gm_win_max.p);
-  a.h_tag = static_cast<wx_u64 *>(w.g_tag.p);
-  a.h_cnt = static_cast<wx_u64 *>(w.g_cnt.p);
-  a.h_used = static_cast<wx_u32 *>(w.g_used.p);
-  a.h_sum = static_cast<double *>(w.gm_sum.p);
-  a.h_min = static_cast<wx_u32 *>(w.gm_min.p);
-  a.h_max = static_cast<wx_u32 *>(w.gm_max.p);
-  a.ctrs = static_cast<wx_u64 *>(w.g_ctrs.p);
-  a.hmask = (wx_u32)(hcap - 1);
-  a.key_lo = key_lo;
+  a.acc = group_planes(w, op.s, ns, nq, capacity, key_lo);
   WxGroupMultiFinArgs f{};
-  f.win_cnt = a.win_cnt;
-  f.win_sum = a.win_sum;
-  f.win_min = a.win_min;
-  f.win_max = a.win_max;
-  f.h_tag = a.h_tag;
-  f.h_cnt = a.h_cnt;
-  f.h_used = a.h_used;
-  f.h_sum = a.h_sum;
-  f.h_min = a.h_min;
-  f.h_max = a.h_max;
-  f.ctrs = a.ctrs;
-  f.hmask = a.hmask;
-  f.key_lo = key_lo;
+  f.acc = a.acc;
   f.out_keys = d_keys;
   f.out_counts = reinterpret_cast<wx_i64 *>(d_counts);
   for (int32_t j = 0; j < n_vals; ++j) {
@@ -146,34 +97,8 @@ void do_group_multi(const wx_table *t, const char *const *val_exprs, int32_t n_v
     const unsigned grid = grid_for(((t->n_rows + 3) / 4 + f256 - 1) / f256, op.d.cus, WX_GM_PER_CU(ns, nq));
     launch(op.mod->fn("wx_group_multi"), grid, &a, op.s, op.timed, (unsigned)gblock);
   }
-  // More than WX_GROUP_HSORT_MAX general keys (possible only when the caller
-  // allows that many groups): sorted on the device by the util module's
-  // gather + sort, which know the keys only.
-  if (capacity > WX_GROUP_HSORT_MAX && t->n_rows > 0) {
-    int64_t nh = 0;
-    WX_HIP(hipMemcpyAsync(&nh, a.ctrs, 8, hipMemcpyDeviceToHost, op.s));
-    WX_HIP(hipStreamSynchronize(op.s));
-    if (nh > WX_GROUP_HSORT_MAX) {
-      int64_t npad = WX_SORT_LDS;
-      while (npad < nh) npad <<= 1;
-      ensure(w, w.g_sorted, (size_t)npad * 8, false);
-      WxGroupGatherArgs ga;
-      ga.ctrs = a.ctrs;
-      ga.h_used = a.h_used;
-      ga.h_tag = a.h_tag;
-      ga.keys = static_cast<wx_u64 *>(w.g_sorted.p);
-      ga.npad = npad;
-      launch(util_module(L.device, true)->fn("wx_group_gather_keys"), grid_for(npad, op.d.cus, 8), &ga, op.s);
-      bitonic_u64(L.device, ga.keys, npad, op.s);
-      f.sorted = ga.keys;
-    }
-  }
-  launch(op.mod->fn("wx_group_multi_finalize"), 1, &f, op.s, false, 1024);  // WX_GMF_BLOCK
-  if (h_n_groups) {  // read before the error check: a capacity error still reports the count
-    WX_HIP(hipStreamSynchronize(op.s));
-    WX_HIP(hipMemcpy(h_n_groups, ng, 8, hipMemcpyDeviceToHost));
-  }
-  if ((L.flags & WX_F_SYNC) || h_n_groups) check_errors(w);
+  f.sorted = sort_general_keys(op, nullptr, a.acc.ctrs, a.acc.h_used, a.acc.h_tag, capacity, t->n_rows > 0);
+  finish_group(op, op.mod->fn("wx_group_multi_finalize"), &f, ng, h_n_groups);
 }
 
 }  // namespace wx

@@ -68,37 +68,10 @@ void do_join_group(const wx_table *left, const wx_table *right, const char *left
   const std::shared_ptr<Module> mod = get_module(L.device, spec, true);
   const int ns = popcount4(smask), nq = popcount4(qmask);
   const int gblock = WX_JG_BLOCK(ns, nq, jt.plan.form);
-  // the accumulators, exactly as do_group_multi ensures them
-  ensure_group_table(w, op.s, next_pow2(std::max<int64_t>(4096, 2 * capacity)));
-  const size_t hcap = w.g_hcap;
-  ensure(w, w.g_win_cnt, WX_GROUP_WINDOW * 8, true);
-  ensure(w, w.g_ctrs, 64, true);
-  if (ns) {
-    ensure_planes(w, op.s, w.gm_win_sum, (size_t)ns * WX_GROUP_WINDOW * 8, 0);
-    ensure_planes(w, op.s, w.gm_sum, (size_t)ns * hcap * 8, 0);
-  }
-  if (nq) {
-    ensure_planes(w, op.s, w.gm_win_min, (size_t)nq * WX_GROUP_WINDOW * 4, 0xff);
-    ensure_planes(w, op.s, w.gm_win_max, (size_t)nq * WX_GROUP_WINDOW * 4, 0);
-    ensure_planes(w, op.s, w.gm_min, (size_t)nq * hcap * 4, 0xff);
-    ensure_planes(w, op.s, w.gm_max, (size_t)nq * hcap * 4, 0);
-  }
   WxJoinGroupArgs a{};
   fill_cols(left, spec.cols, a.g.col);
   a.g.n_rows = left->n_rows;
-  a.g.win_cnt = static_cast<wx_u64 *>(w.g_win_cnt.p);
-  a.g.win_sum = static_cast<double *>(w.gm_win_sum.p);
-  a.g.win_min = static_cast<wx_u32 *>(w.gm_win_min.p);
-  a.g.win_max = static_cast<wx_u32 *>(w.gm_win_max.p);
-  a.g.h_tag = static_cast<wx_u64 *>(w.g_tag.p);
-  a.g.h_cnt = static_cast<wx_u64 *>(w.g_cnt.p);
-  a.g.h_used = static_cast<wx_u32 *>(w.g_used.p);
-  a.g.h_sum = static_cast<double *>(w.gm_sum.p);
-  a.g.h_min = static_cast<wx_u32 *>(w.gm_min.p);
-  a.g.h_max = static_cast<wx_u32 *>(w.gm_max.p);
-  a.g.ctrs = static_cast<wx_u64 *>(w.g_ctrs.p);
-  a.g.hmask = (wx_u32)(hcap - 1);
-  a.g.key_lo = key_lo;
+  a.g.acc = group_planes(w, op.s, ns, nq, capacity, key_lo);
   a.c.ctrs = static_cast<wx_u64 *>(w.ctrs.p);
   fill_cols(right, spec.rcols, a.rcol);
   a.rows = static_cast<const int *>(w.jn_rows.p);
@@ -108,19 +81,7 @@ void do_join_group(const wx_table *left, const wx_table *right, const char *left
   a.mask = jt.mask;
   a.shift = jt.shift;
   WxGroupMultiFinArgs f{};
-  f.win_cnt = a.g.win_cnt;
-  f.win_sum = a.g.win_sum;
-  f.win_min = a.g.win_min;
-  f.win_max = a.g.win_max;
-  f.h_tag = a.g.h_tag;
-  f.h_cnt = a.g.h_cnt;
-  f.h_used = a.g.h_used;
-  f.h_sum = a.g.h_sum;
-  f.h_min = a.g.h_min;
-  f.h_max = a.g.h_max;
-  f.ctrs = a.g.ctrs;
-  f.hmask = a.g.hmask;
-  f.key_lo = key_lo;
+  f.acc = a.g.acc;
   f.out_keys = d_keys;
   f.out_counts = reinterpret_cast<wx_i64 *>(d_counts);
   for (int32_t j = 0; j < n_vals; ++j) {
@@ -137,33 +98,8 @@ void do_join_group(const wx_table *left, const wx_table *right, const char *left
                                    WX_JG_PER_CU(ns, nq, jt.plan.form));
     launch(mod->fn("wx_join_group"), grid, &a, op.s, op.timed, (unsigned)gblock);
   }
-  // More than WX_GROUP_HSORT_MAX general keys: sorted on the device by the
-  // util module's gather and sort, as do_group_multi does.
-  if (capacity > WX_GROUP_HSORT_MAX) {
-    int64_t nh = 0;
-    WX_HIP(hipMemcpyAsync(&nh, a.g.ctrs, 8, hipMemcpyDeviceToHost, op.s));
-    WX_HIP(hipStreamSynchronize(op.s));
-    if (nh > WX_GROUP_HSORT_MAX) {
-      int64_t npad = WX_SORT_LDS;
-      while (npad < nh) npad <<= 1;
-      ensure(w, w.g_sorted, (size_t)npad * 8, false);
-      WxGroupGatherArgs ga;
-      ga.ctrs = a.g.ctrs;
-      ga.h_used = a.g.h_used;
-      ga.h_tag = a.g.h_tag;
-      ga.keys = static_cast<wx_u64 *>(w.g_sorted.p);
-      ga.npad = npad;
-      launch(util_module(L.device, true)->fn("wx_group_gather_keys"), grid_for(npad, op.d.cus, 8), &ga, op.s);
-      bitonic_u64(L.device, ga.keys, npad, op.s);
-      f.sorted = ga.keys;
-    }
-  }
-  launch(mod->fn("wx_group_multi_finalize"), 1, &f, op.s, false, 1024);  // WX_GMF_BLOCK
-  if (h_n_groups) {  // read before the error check: a capacity error still reports the count
-    WX_HIP(hipStreamSynchronize(op.s));
-    WX_HIP(hipMemcpy(h_n_groups, ng, 8, hipMemcpyDeviceToHost));
-  }
-  if ((L.flags & WX_F_SYNC) || h_n_groups) check_errors(w);
+  f.sorted = sort_general_keys(op, nullptr, a.g.acc.ctrs, a.g.acc.h_used, a.g.acc.h_tag, capacity, true);
+  finish_group(op, mod->fn("wx_group_multi_finalize"), &f, ng, h_n_groups);
 }
 
 }  // namespace wx

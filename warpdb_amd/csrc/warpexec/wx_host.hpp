@@ -469,8 +469,14 @@ void do_group_multi(const wx_table *t, const char *const *val_exprs, int32_t n_v
                     const char *cond, const wx_launch *Lp, int32_t key_lo, int64_t capacity, int32_t *d_keys,
                     double *const *d_sums, int64_t *d_counts, float *const *d_mins, float *const *d_maxs,
                     int64_t *d_n_groups, int64_t *h_n_groups);
+
+// group_window.cpp: shared by the LDS-window GROUP BY families
 int popcount4(int m);
 void ensure_planes(Workspace &w, hipStream_t s, Buf &b, size_t bytes, int fill);
+WxGroupPlanes group_planes(Workspace &w, hipStream_t s, int ns, int nq, int64_t capacity, int key_lo);
+const wx_u64 *sort_general_keys(Op &op, Module *own, wx_u64 *ctrs, wx_u32 *h_used, wx_u64 *h_tag, int64_t capacity,
+                                bool any_rows);
+void finish_group(Op &op, hipFunction_t finalize, void *fin_args, int64_t *ng, int64_t *h_n_groups);
 
 // group_rows.cpp
 void do_group_sum_rows(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond,
