@@ -653,6 +653,42 @@ wx_status wx_group_part_geometry(int64_t n_rows, int64_t key_span, int32_t cus, 
  * range (an aborted pass followed by the window + hash also counts 1). */
 wx_status wx_group_part_passes(const wx_launch *launch, int64_t *passes, char *err, size_t errlen);
 
+/* The launch geometry of the streaming kernel of an LDS-window GROUP BY over
+ * n_rows rows with n_sums summed and n_minmax MIN / MAX values, under the
+ * current diagnostic define list (WX_GROUP_GRID=<g> caps the grid and changes
+ * nothing else, WX_UNROLL, WX_GROUP_LEAD; WARPDB_EXTRA_DEFINES): the same
+ * arithmetic as the run path's.  family: wx_group_sum / wx_group_agg (one
+ * sum, n_minmax 0 or 1), wx_group_agg_multi, or wx_join_group_agg in the
+ * join form join_form (0 direct, 1 hash; ignored otherwise).  cus > 0: a
+ * device of that many compute units (needs no device); cus <= 0: the
+ * launch's device.  With q = row >> 2 and span = span_rows / 4 quads, row
+ * `row` is element row & 3 of thread q % block_threads in round (q % span) /
+ * block_threads of batch (q / span) / grid of workgroup (q / span) % grid.
+ * An argument or define out of range (WX_GROUP_GRID < 1) is WX_ERR_INVALID. */
+#define WX_GW_GROUP_SUM 0
+#define WX_GW_GROUP_MULTI 1
+#define WX_GW_JOIN_GROUP 2
+typedef struct wx_group_window_geom {
+  int64_t block_threads; /* threads per workgroup */
+  int64_t span_rows;     /* rows of one batch span */
+  int64_t grid;          /* workgroups */
+  int64_t max_batches;   /* the most batches any workgroup runs */
+  int64_t window_keys;   /* keys of the LDS window (WX_GROUP_WINDOW_BINS) */
+  int64_t hsort_max;     /* most general keys the finalize sorts in LDS; more are sorted on the device */
+  int64_t lead;          /* lanes of a wave on one window bin from which they add once (0: the build has no such add) */
+} wx_group_window_geom;
+wx_status wx_group_window_geometry(int64_t n_rows, int32_t n_sums, int32_t n_minmax, int32_t family,
+                                   int32_t join_form, int32_t cus, const wx_launch *launch, wx_group_window_geom *out,
+                                   char *err, size_t errlen);
+/* Slots of the general-key table (keys outside the window) of the launch's
+ * (device, stream) as it stands: a power of two that only grows, 0 before the
+ * first GROUP BY there.  A plain host number (no device read). */
+wx_status wx_group_table_slots(const wx_launch *launch, int64_t *slots, char *err, size_t errlen);
+/* The home slot of a key in a general-key table of `slots` slots (a power of
+ * two up to 2^30), as the kernels compute it; probing goes on to the next
+ * slot, wrapping.  -1 when `slots` is not such a number. */
+int32_t wx_group_hash_slot(int32_t key, int64_t slots);
+
 /* One shard's ORDER BY .. LIMIT candidates in the exchange layout (520 bytes):
  * wx_topk's d_keys / d_vals / d_idx / d_count pointed at keys, vals, rows and
  * count fill it, so the records of all shards are one all-gather of bytes. */

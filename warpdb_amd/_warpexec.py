@@ -66,6 +66,7 @@ GROUP_MAX_VALUES = 4  # WX_GROUP_MAX_VALUES  # WX_MAX_OUTPUTS: expressions of on
 WIN_SUM, WIN_AVG, WIN_COUNT, WIN_MIN, WIN_MAX = 0, 1, 2, 3, 4  # wx_window_item.agg
 JOIN_INNER, JOIN_LEFT = 0, 1  # wx_join_select's join_type
 JOIN_DIRECT, JOIN_HASH = 0, 1  # the form of a join's table (wx_join_plan)
+GW_GROUP_SUM, GW_GROUP_MULTI, GW_JOIN_GROUP = 0, 1, 2  # wx_group_window_geometry's family
 JOIN_DIRECT_BINS = 4096  # widest key span of the direct form
 JOIN_MAX_RIGHT = 1 << 26  # most rows of a right table
 
@@ -111,6 +112,9 @@ EXPORTED_SYMBOLS = (
     "wx_topk_plan",
     "wx_group_part_geometry",
     "wx_group_part_passes",
+    "wx_group_window_geometry",
+    "wx_group_table_slots",
+    "wx_group_hash_slot",
     "wx_sort_pairs",
     "wx_sort_float",
     "wx_sort_float_from",
@@ -156,6 +160,11 @@ class WxGroupPartGeometry(ctypes.Structure):
     _fields_ = [(f, ctypes.c_int64) for f in (
         "tile_rows", "n_tiles", "grid", "tiles_per_wg", "n_part", "part_keys", "chunk_rows", "target_items",
         "work_cap", "dir_chunk", "agg_tiles_per_sweep")]
+
+
+class WxGroupWindowGeometry(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_int64) for f in (
+        "block_threads", "span_rows", "grid", "max_batches", "window_keys", "hsort_max", "lead")]
 
 
 class WxCompactGeometry(ctypes.Structure):
@@ -239,6 +248,8 @@ def load() -> ctypes.CDLL:
         "wx_topk_plan": [I64, I32, I32, L, ctypes.POINTER(WxTopkGeometry), E, S],
         "wx_group_part_geometry": [I64, I64, I32, L, ctypes.POINTER(WxGroupPartGeometry), E, S],
         "wx_group_part_passes": [L, pI64, E, S],
+        "wx_group_window_geometry": [I64, I32, I32, I32, I32, I32, L, ctypes.POINTER(WxGroupWindowGeometry), E, S],
+        "wx_group_table_slots": [L, pI64, E, S],
         "wx_compact_last_launch": [L, ctypes.POINTER(WxCompactGeometry), E, S],
         "wx_sort_pairs": [P, P, I64, I32, L, E, S],
         "wx_sort_float": [P, I64, I32, L, E, S],
@@ -268,6 +279,8 @@ def load() -> ctypes.CDLL:
     lib.wx_join_tile_rows.restype = ctypes.c_int32
     lib.wx_join_hash_slot.argtypes = [I32, I32]
     lib.wx_join_hash_slot.restype = ctypes.c_int32
+    lib.wx_group_hash_slot.argtypes = [I32, I64]
+    lib.wx_group_hash_slot.restype = ctypes.c_int32
     lib.wx_gather_tile_rows.argtypes = [I32]
     lib.wx_gather_tile_rows.restype = ctypes.c_int32
     lib.wx_sort_tile_keys.argtypes = [I32]
@@ -478,7 +491,11 @@ def group_sum(table: Table, val_expr: str, key_expr: str, cond: Optional[str], l
                           ctypes.byref(launch), key_window_lo, capacity, d_keys or None, d_sums or None,
                           d_counts or None, d_n_groups or None, ctypes.byref(h) if want_count else None,
                           err, len(err))
-    _check(st, err)
+    try:
+        _check(st, err)
+    except WarpExecError as e:
+        e.count = h.value  # on WX_ERR_CAPACITY: the number of groups found
+        raise
     return h.value if want_count else None
 
 
@@ -504,7 +521,11 @@ def group_agg(table: Table, val_expr: str, key_expr: str, cond: Optional[str], l
                           ctypes.byref(launch), key_window_lo, capacity, d_keys or None, d_sums or None,
                           d_counts or None, d_mins or None, d_maxs or None, d_n_groups or None,
                           ctypes.byref(h) if want_count else None, err, len(err))
-    _check(st, err)
+    try:
+        _check(st, err)
+    except WarpExecError as e:
+        e.count = h.value  # on WX_ERR_CAPACITY: the number of groups found
+        raise
     return h.value if want_count else None
 
 
@@ -873,6 +894,39 @@ def group_part_passes(launch: WxLaunch) -> int:
     n = ctypes.c_int64(-1)
     _check(lib.wx_group_part_passes(ctypes.byref(launch), ctypes.byref(n), err, len(err)), err)
     return n.value
+
+
+def group_window_geometry(n_rows: int, n_sums: int, n_minmax: int, family: int = GW_GROUP_SUM,
+                          join_form: int = JOIN_HASH, cus: int = 0,
+                          launch: Optional[WxLaunch] = None) -> WxGroupWindowGeometry:
+    """The launch geometry of the streaming kernel of an LDS-window GROUP BY
+    (family GW_GROUP_SUM / GW_GROUP_MULTI / GW_JOIN_GROUP) under the current
+    WARPDB_EXTRA_DEFINES (WX_GROUP_GRID, WX_UNROLL, WX_GROUP_LEAD):
+    .block_threads, .span_rows, .grid, .max_batches (of the workgroup that
+    runs the most), .window_keys, .hsort_max, .lead.  cus > 0 names the
+    device's compute units (no device needed); otherwise the launch's device."""
+    lib = load()
+    err = _err()
+    out = WxGroupWindowGeometry()
+    _check(lib.wx_group_window_geometry(n_rows, n_sums, n_minmax, family, join_form, cus,
+                                        ctypes.byref(launch) if launch is not None else None, ctypes.byref(out), err,
+                                        len(err)), err)
+    return out
+
+
+def group_table_slots(launch: WxLaunch) -> int:
+    """Slots of the general-key table of the launch's (device, stream) as it
+    stands (a host number; 0 before the first GROUP BY there)."""
+    lib = load()
+    err = _err()
+    n = ctypes.c_int64(-1)
+    _check(lib.wx_group_table_slots(ctypes.byref(launch), ctypes.byref(n), err, len(err)), err)
+    return n.value
+
+
+def group_hash_slot(key: int, slots: int) -> int:
+    """The home slot the kernels use for `key` in a general-key table of `slots` slots (-1: not a power of two)."""
+    return int(load().wx_group_hash_slot(key, slots))
 
 
 def sort_pairs(d_keys: int, d_vals: int, count: int, ascending: bool, launch: WxLaunch) -> None:

@@ -42,9 +42,6 @@ int64_t gp_tile_rows() { return (int64_t)WX_GP_TBLOCK * 4 * gp_sunroll(); }
 int gp_shift() { return 13; }
 int64_t gp_max_span() { return (int64_t)WX_GP_STAGE_MAX_PARTS << gp_shift(); }
 
-// wx_group_sum's workgroup size (512 at two per CU: profiles/r03/abl_group_grid.txt)
-int gp_gblock() { return WX_GBLOCK; }
-
 // The launch geometry of one partitioned pass over n_rows rows and a key
 // span of `span`: the one statement of it (group_partitioned launches it,
 // wx_group_part_geometry reports it).  One 1024-thread tile workgroup per CU
@@ -300,7 +297,6 @@ void do_group_sum(const wx_table *t, const char *val_expr, const char *key_expr,
     fail(WX_ERR_INVALID, "group outputs must hold `capacity` entries");
   if ((int64_t)key_lo + WX_GROUP_WINDOW - 1 > INT32_MAX) fail(WX_ERR_INVALID, "key window out of range");
   const Spec spec = group_spec(t, val_expr, key_expr, cond, L, minmax);
-  const int gblock = gp_gblock();
   Op op(L, spec);
   // the general-key table must hold every distinct key outside the window
   ensure_group_table(op.w, op.s, next_pow2(std::max<int64_t>(4096, 2 * capacity)));
@@ -426,9 +422,8 @@ void do_group_sum(const wx_table *t, const char *val_expr, const char *key_expr,
   f.slot_rank = slot_rank;
   f.slot_groups = slot_groups;
   if (t->n_rows > 0) {
-    const int gpc = 4 * WX_BLOCK / gblock;  // 16 waves per CU
-    const unsigned grid = grid_for(((t->n_rows + 3) / 4 + gblock / WX_BLOCK - 1) / (gblock / WX_BLOCK), op.d.cus, gpc);
-    launch(op.mod->fn("wx_group_sum"), grid, &a, op.s, op.timed, (unsigned)gblock);
+    const GroupWindowPlan P = group_window_plan(t->n_rows, 1, minmax ? 1 : 0, WX_GW_GROUP_SUM, 0, op.d.cus, spec.extra);
+    launch(op.mod->fn("wx_group_sum"), P.grid, &a, op.s, op.timed, (unsigned)P.block);
   }
   f.sorted = sort_general_keys(op, op.mod.get(), a.ctrs, a.h_used, a.h_tag, capacity, t->n_rows > 0);
   finish_group(op, op.mod->fn("wx_group_finalize"), &f, ng, h_n_groups);

@@ -38,7 +38,6 @@ void do_group_multi(const wx_table *t, const char *const *val_exprs, int32_t n_v
   if ((int64_t)key_lo + WX_GROUP_WINDOW - 1 > INT32_MAX) fail(WX_ERR_INVALID, "key window out of range");
   const Spec spec = group_multi_spec(t, val_exprs, n_vals, smask, qmask, key_expr, cond, L);
   const int ns = popcount4(smask), nq = popcount4(qmask);
-  const int gblock = WX_GM_BLOCK(ns, nq);
   Op op(L, spec);
   Workspace &w = op.w;
   int64_t *ng = count_slot(w, w.g_ngroups, d_n_groups);
@@ -93,9 +92,8 @@ void do_group_multi(const wx_table *t, const char *const *val_exprs, int32_t n_v
   f.capacity = capacity;
   if (t->n_rows > 0) {
     // 16 waves per CU (WX_GM_PER_CU workgroups of WX_GM_BLOCK threads), one row quad per thread
-    const int f256 = gblock / WX_BLOCK;
-    const unsigned grid = grid_for(((t->n_rows + 3) / 4 + f256 - 1) / f256, op.d.cus, WX_GM_PER_CU(ns, nq));
-    launch(op.mod->fn("wx_group_multi"), grid, &a, op.s, op.timed, (unsigned)gblock);
+    const GroupWindowPlan P = group_window_plan(t->n_rows, ns, nq, WX_GW_GROUP_MULTI, 0, op.d.cus, spec.extra);
+    launch(op.mod->fn("wx_group_multi"), P.grid, &a, op.s, op.timed, (unsigned)P.block);
   }
   f.sorted = sort_general_keys(op, nullptr, a.acc.ctrs, a.acc.h_used, a.acc.h_tag, capacity, t->n_rows > 0);
   finish_group(op, op.mod->fn("wx_group_multi_finalize"), &f, ng, h_n_groups);

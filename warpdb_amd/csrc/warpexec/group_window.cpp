@@ -8,6 +8,55 @@ namespace wx {
 
 int popcount4(int m) { return (m & 1) + ((m >> 1) & 1) + ((m >> 2) & 1) + ((m >> 3) & 1); }
 
+// The launch geometry of the streaming kernel of one LDS-window GROUP BY
+// over n_rows rows: the one statement of it (do_group_sum, do_group_multi and
+// do_join_group launch it, wx_group_window_geometry reports it).  ns summed
+// and nq MIN / MAX values; family WX_GW_GROUP_SUM (wx_group_sum, with
+// WX_MINMAX when nq == 1), WX_GW_GROUP_MULTI or WX_GW_JOIN_GROUP in the join
+// form `form`.  One workgroup per `block` row quads up to 16 waves per CU;
+// workgroup b runs the spans b, b + grid, ... of block * WX_UNROLL quads
+// each, one batch per span.  WX_GROUP_GRID=<g> (diagnostic define) caps the
+// grid and changes nothing else, so that a small table runs many batches per
+// workgroup.
+GroupWindowPlan group_window_plan(int64_t n_rows, int ns, int nq, int family, int form, int cus,
+                                  const std::string &extra) {
+  if (n_rows < 0) fail(WX_ERR_INVALID, "negative row count");
+  if (cus < 1) fail(WX_ERR_INVALID, "GROUP BY: no compute units");
+  if (ns < 0 || ns > WX_GM_MAX || nq < 0 || nq > WX_GM_MAX || ns + nq < 1)
+    fail(WX_ERR_INVALID, "n_sums and n_minmax must be between 0 and " + std::to_string(WX_GM_MAX) +
+                             ", and one of them at least 1");
+  GroupWindowPlan P;
+  int per_cu = 0;
+  if (family == WX_GW_GROUP_SUM) {
+    if (ns != 1 || nq > 1) fail(WX_ERR_INVALID, "wx_group_sum carries one sum and at most one MIN / MAX");
+    P.block = WX_GBLOCK;                // 512 at two per CU: profiles/r03/abl_group_grid.txt
+    per_cu = 4 * WX_BLOCK / WX_GBLOCK;  // 16 waves per CU
+  } else if (family == WX_GW_GROUP_MULTI) {
+    P.block = WX_GM_BLOCK(ns, nq);
+    per_cu = WX_GM_PER_CU(ns, nq);
+  } else if (family == WX_GW_JOIN_GROUP) {
+    if (form != WX_JOIN_FORM_DIRECT && form != WX_JOIN_FORM_HASH)
+      fail(WX_ERR_INVALID, "form must be 0 (direct) or 1 (hash)");
+    P.block = WX_JG_BLOCK(ns, nq, form);
+    per_cu = WX_JG_PER_CU(ns, nq, form);
+  } else {
+    fail(WX_ERR_INVALID, "family must be 0 (group_sum), 1 (group_multi) or 2 (join_group)");
+  }
+  const int cap = define_value(extra, "WX_GROUP_GRID", INT32_MAX);
+  if (cap < 1) fail(WX_ERR_INVALID, "WX_GROUP_GRID must be at least 1");
+  const int unroll = define_value(extra, "WX_UNROLL", 2);  // the kernels' default
+  if (unroll < 1) fail(WX_ERR_INVALID, "WX_UNROLL must be at least 1");
+  const int f256 = P.block / WX_BLOCK;
+  const int64_t nq4 = (n_rows + 3) / 4;
+  P.grid = std::min<unsigned>(grid_for((nq4 + f256 - 1) / f256, cus, per_cu), (unsigned)cap);
+  const int64_t span = (int64_t)P.block * unroll;
+  P.span_rows = span * 4;
+  // workgroup 0 runs the most batches: every grid-th of the span positions
+  P.max_batches = ((nq4 + span - 1) / span + P.grid - 1) / P.grid;
+  P.lead = nq ? 0 : define_value(extra, "WX_GROUP_LEAD", 16);  // sum-only builds carry the wave-combined add
+  return P;
+}
+
 // A plane buffer of at least `bytes`, every byte `fill` when freshly
 // allocated: the finalize leaves the planes idle, so an old one is as it
 // should be.

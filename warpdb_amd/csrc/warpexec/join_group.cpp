@@ -67,7 +67,6 @@ void do_join_group(const wx_table *left, const wx_table *right, const char *left
                                     group_key_expr, cond, L);
   const std::shared_ptr<Module> mod = get_module(L.device, spec, true);
   const int ns = popcount4(smask), nq = popcount4(qmask);
-  const int gblock = WX_JG_BLOCK(ns, nq, jt.plan.form);
   WxJoinGroupArgs a{};
   fill_cols(left, spec.cols, a.g.col);
   a.g.n_rows = left->n_rows;
@@ -93,10 +92,9 @@ void do_join_group(const wx_table *left, const wx_table *right, const char *left
   f.capacity = capacity;
   {
     // 16 waves per CU (WX_JG_PER_CU workgroups of WX_JG_BLOCK threads), one row quad per thread
-    const int f256 = gblock / WX_BLOCK;
-    const unsigned grid = grid_for(((left->n_rows + 3) / 4 + f256 - 1) / f256, op.d.cus,
-                                   WX_JG_PER_CU(ns, nq, jt.plan.form));
-    launch(mod->fn("wx_join_group"), grid, &a, op.s, op.timed, (unsigned)gblock);
+    const GroupWindowPlan P =
+        group_window_plan(left->n_rows, ns, nq, WX_GW_JOIN_GROUP, jt.plan.form, op.d.cus, spec.extra);
+    launch(mod->fn("wx_join_group"), P.grid, &a, op.s, op.timed, (unsigned)P.block);
   }
   f.sorted = sort_general_keys(op, nullptr, a.g.acc.ctrs, a.g.acc.h_used, a.g.acc.h_tag, capacity, true);
   finish_group(op, mod->fn("wx_group_multi_finalize"), &f, ng, h_n_groups);

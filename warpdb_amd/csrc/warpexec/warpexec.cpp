@@ -417,6 +417,37 @@ wx_status wx_group_part_passes(const wx_launch *launch_, int64_t *passes, char *
   });
 }
 
+wx_status wx_group_window_geometry(int64_t n_rows, int32_t n_sums, int32_t n_minmax, int32_t family,
+                                   int32_t join_form, int32_t cus, const wx_launch *launch_, wx_group_window_geom *out,
+                                   char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    if (!out) fail(WX_ERR_INVALID, "null geometry output");
+    if (cus <= 0) cus = device_state(launch_of(launch_).device, true).cus;
+    const GroupWindowPlan P =
+        group_window_plan(n_rows, n_sums, n_minmax, family, join_form, cus, env_or("WARPDB_EXTRA_DEFINES", ""));
+    out->block_threads = P.block;
+    out->span_rows = P.span_rows;
+    out->grid = P.grid;
+    out->max_batches = P.max_batches;
+    out->window_keys = WX_GROUP_WINDOW;
+    out->hsort_max = WX_GROUP_HSORT_MAX;
+    out->lead = P.lead;
+  });
+}
+
+wx_status wx_group_table_slots(const wx_launch *launch_, int64_t *slots, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    if (!slots) fail(WX_ERR_INVALID, "null slot count output");
+    Op op(launch_of(launch_));
+    *slots = op.w.g_hcap;
+  });
+}
+
+int32_t wx_group_hash_slot(int32_t key, int64_t slots) {
+  if (slots < 1 || slots > (1ll << 30) || (slots & (slots - 1))) return -1;
+  return (int32_t)(((uint32_t)key * 2654435761u) & (uint32_t)(slots - 1));
+}
+
 wx_status wx_sort_pairs(int32_t *d_keys, float *d_vals, int64_t count, int32_t ascending, const wx_launch *launch_,
                         char *err, size_t errlen) {
   return guarded(err, errlen, [&] { do_sort(d_keys, d_vals, count, 1, ascending, launch_); });

@@ -472,6 +472,15 @@ void do_group_multi(const wx_table *t, const char *const *val_exprs, int32_t n_v
 
 // group_window.cpp: shared by the LDS-window GROUP BY families
 int popcount4(int m);
+struct GroupWindowPlan {
+  int block = 0;            // threads per workgroup
+  int64_t span_rows = 0;    // rows of one batch span (block * WX_UNROLL quads)
+  unsigned grid = 1;        // workgroups of the streaming kernel
+  int64_t max_batches = 0;  // batches of the workgroup that runs the most
+  int lead = 0;             // WX_GROUP_LEAD of the build (0: no wave-combined add)
+};
+GroupWindowPlan group_window_plan(int64_t n_rows, int ns, int nq, int family, int form, int cus,
+                                  const std::string &extra);
 void ensure_planes(Workspace &w, hipStream_t s, Buf &b, size_t bytes, int fill);
 WxGroupPlanes group_planes(Workspace &w, hipStream_t s, int ns, int nq, int64_t capacity, int key_lo);
 const wx_u64 *sort_general_keys(Op &op, Module *own, wx_u64 *ctrs, wx_u32 *h_used, wx_u64 *h_tag, int64_t capacity,
