@@ -653,6 +653,66 @@ wx_status wx_group_part_geometry(int64_t n_rows, int64_t key_span, int32_t cus, 
  * range (an aborted pass followed by the window + hash also counts 1). */
 wx_status wx_group_part_passes(const wx_launch *launch, int64_t *passes, char *err, size_t errlen);
 
+/* The sizes the row-order GROUP BY (WX_F_ROW_ORDER) works in, from which its
+ * tests size their tables.  Needs no device.  fold_block_values and
+ * fold_blocks_ahead follow the diagnostic define list (WX_XF_J, WX_XF_AHEAD of
+ * WARPDB_EXTRA_DEFINES); the rest are fixed. */
+typedef struct wx_group_rows_geom {
+  int64_t tile_rows;          /* rows of one tile of the span path's scatter */
+  int64_t span_bins;          /* bins of the span path: the widest key span it takes */
+  int64_t count_span_rows;    /* rows of one span of the count kernel's loop */
+  int64_t fold_block_values;  /* values of one block of the exact fold */
+  int64_t fold_blocks_ahead;  /* blocks the exact fold keeps in flight */
+  int64_t fold_small;         /* general path: largest group folded by one lane (WARPDB_FOLD_SMALL overrides) */
+  int64_t starts_chunk;       /* general path after the ordinary call: groups per chunk of the start scan */
+  int64_t rle_wave_rows;      /* general path without it: sorted rows one wave run-length encodes */
+  int64_t xf_chunk;           /* values of one chunk of a group folded in chunks */
+  int64_t xf_big;             /* groups of more rows are folded in chunks (WARPDB_XF_BIG overrides) */
+  int64_t sample_rows;        /* rows the direct span path samples (thread i: row i * n_rows / sample_rows) */
+} wx_group_rows_geom;
+wx_status wx_group_rows_geometry(wx_group_rows_geom *out, char *err, size_t errlen);
+
+/* What the last WX_F_ROW_ORDER call on the launch's (device, stream) did:
+ * plain host numbers (no device read, no synchronisation).  All zero before
+ * any such call, after one that failed, and after one whose ordinary call
+ * found no group.  The span path runs `ranges` workgroups over static ranges
+ * of whole tiles, min(tiles, 2 * compute units) of them; the diagnostic
+ * variable WARPDB_RO_RANGES=<n> (an integer >= 1, else WX_ERR_INVALID from
+ * the grouping call) caps that number, so that one workgroup runs many tiles
+ * in order.  It changes no result. */
+#define WX_RO_ROUTE_NONE 0
+#define WX_RO_ROUTE_DIRECT 1           /* the span path straight from the table */
+#define WX_RO_ROUTE_ORDINARY_SPAN 2    /* the ordinary call, then the span path over its exact key range */
+#define WX_RO_ROUTE_GENERAL_RUNS 3     /* sort + fold, the groups from the sorted keys' runs */
+#define WX_RO_ROUTE_GENERAL_ORDINARY 4 /* the ordinary call, then sort + fold over its groups */
+#define WX_RO_WHY_NONE 0       /* the direct span path was taken */
+#define WX_RO_WHY_RECENT_MISS 1 /* it missed within the last 16 calls over these expressions and table */
+#define WX_RO_WHY_NO_SAMPLE 2  /* no sampled row passed the WHERE */
+#define WX_RO_WHY_OUTSIDE 3    /* a passing row's key lay outside the guessed span */
+#define WX_RO_WHY_WIDE 4       /* the sampled (or remembered) keys span more than span_bins */
+#define WX_RO_WHY_NOT_TRIED 5  /* MIN / MAX asked, WARPDB_GROUP_ROWS, or a device without lane-ordered LDS adds */
+typedef struct wx_group_rows_record {
+  int64_t route;      /* WX_RO_ROUTE_* */
+  int64_t why;        /* WX_RO_WHY_*: why the direct span path was not taken */
+  int64_t ranges;     /* span routes: workgroups (ranges of tiles) launched; else 0 */
+  int64_t tiles;      /* span routes: tiles of the table; else 0 */
+  int64_t n_values;   /* length of the row-ordered value array (the passing rows) */
+  int64_t big_groups; /* groups folded in chunks */
+  int64_t big_chunks; /* their chunks */
+} wx_group_rows_record;
+wx_status wx_group_rows_last_call(const wx_launch *launch, wx_group_rows_record *out, char *err, size_t errlen);
+/* Copies the last WX_F_ROW_ORDER call's row-ordered value array -- the
+ * passing rows' values, key-major, ascending row order within a key: the
+ * span routes' scatter output, the general routes' sorted payload where the
+ * last sort pass left it -- into d_out (device, `capacity` floats), device to
+ * device on the launch's stream (synchronous with WX_F_SYNC), and gives its
+ * length in n_values (nullable).  The array lives in the workspace and is
+ * valid until the next call on that (device, stream).  WX_ERR_INVALID when
+ * no such call ran (route WX_RO_ROUTE_NONE), WX_ERR_CAPACITY when it holds
+ * more than `capacity` values (n_values is still given). */
+wx_status wx_group_rows_last_values(const wx_launch *launch, float *d_out, int64_t capacity, int64_t *n_values,
+                                    char *err, size_t errlen);
+
 /* The launch geometry of the streaming kernel of an LDS-window GROUP BY over
  * n_rows rows with n_sums summed and n_minmax MIN / MAX values, under the
  * current diagnostic define list (WX_GROUP_GRID=<g> caps the grid and changes

@@ -112,6 +112,9 @@ EXPORTED_SYMBOLS = (
     "wx_topk_plan",
     "wx_group_part_geometry",
     "wx_group_part_passes",
+    "wx_group_rows_geometry",
+    "wx_group_rows_last_call",
+    "wx_group_rows_last_values",
     "wx_group_window_geometry",
     "wx_group_table_slots",
     "wx_group_hash_slot",
@@ -165,6 +168,22 @@ class WxGroupPartGeometry(ctypes.Structure):
 class WxGroupWindowGeometry(ctypes.Structure):
     _fields_ = [(f, ctypes.c_int64) for f in (
         "block_threads", "span_rows", "grid", "max_batches", "window_keys", "hsort_max", "lead")]
+
+
+class WxGroupRowsGeometry(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_int64) for f in (
+        "tile_rows", "span_bins", "count_span_rows", "fold_block_values", "fold_blocks_ahead", "fold_small",
+        "starts_chunk", "rle_wave_rows", "xf_chunk", "xf_big", "sample_rows")]
+
+
+class WxGroupRowsRecord(ctypes.Structure):
+    _fields_ = [(f, ctypes.c_int64) for f in (
+        "route", "why", "ranges", "tiles", "n_values", "big_groups", "big_chunks")]
+
+
+# wx_group_rows_record.route / .why
+RO_ROUTE_NONE, RO_ROUTE_DIRECT, RO_ROUTE_ORDINARY_SPAN, RO_ROUTE_GENERAL_RUNS, RO_ROUTE_GENERAL_ORDINARY = range(5)
+RO_WHY_NONE, RO_WHY_RECENT_MISS, RO_WHY_NO_SAMPLE, RO_WHY_OUTSIDE, RO_WHY_WIDE, RO_WHY_NOT_TRIED = range(6)
 
 
 class WxCompactGeometry(ctypes.Structure):
@@ -248,6 +267,9 @@ def load() -> ctypes.CDLL:
         "wx_topk_plan": [I64, I32, I32, L, ctypes.POINTER(WxTopkGeometry), E, S],
         "wx_group_part_geometry": [I64, I64, I32, L, ctypes.POINTER(WxGroupPartGeometry), E, S],
         "wx_group_part_passes": [L, pI64, E, S],
+        "wx_group_rows_geometry": [ctypes.POINTER(WxGroupRowsGeometry), E, S],
+        "wx_group_rows_last_call": [L, ctypes.POINTER(WxGroupRowsRecord), E, S],
+        "wx_group_rows_last_values": [L, P, I64, pI64, E, S],
         "wx_group_window_geometry": [I64, I32, I32, I32, I32, I32, L, ctypes.POINTER(WxGroupWindowGeometry), E, S],
         "wx_group_table_slots": [L, pI64, E, S],
         "wx_compact_last_launch": [L, ctypes.POINTER(WxCompactGeometry), E, S],
@@ -893,6 +915,43 @@ def group_part_passes(launch: WxLaunch) -> int:
     err = _err()
     n = ctypes.c_int64(-1)
     _check(lib.wx_group_part_passes(ctypes.byref(launch), ctypes.byref(n), err, len(err)), err)
+    return n.value
+
+
+def group_rows_geometry() -> WxGroupRowsGeometry:
+    """The sizes the row-order GROUP BY works in (no device needed):
+    .tile_rows, .span_bins, .count_span_rows, .fold_block_values,
+    .fold_blocks_ahead, .fold_small, .starts_chunk, .rle_wave_rows, .xf_chunk,
+    .xf_big, .sample_rows."""
+    lib = load()
+    err = _err()
+    out = WxGroupRowsGeometry()
+    _check(lib.wx_group_rows_geometry(ctypes.byref(out), err, len(err)), err)
+    return out
+
+
+def group_rows_last_call(launch: WxLaunch) -> WxGroupRowsRecord:
+    """What the last F_ROW_ORDER call on the launch's (device, stream) did:
+    .route (RO_ROUTE_*), .why (RO_WHY_*: why not the direct span path),
+    .ranges, .tiles, .n_values, .big_groups, .big_chunks.  Host numbers; all
+    zero before any such call, after a failed one and after one without groups
+    from the ordinary call.  WARPDB_RO_RANGES=<n> caps .ranges."""
+    lib = load()
+    err = _err()
+    out = WxGroupRowsRecord()
+    _check(lib.wx_group_rows_last_call(ctypes.byref(launch), ctypes.byref(out), err, len(err)), err)
+    return out
+
+
+def group_rows_last_values(launch: WxLaunch, d_out: int, capacity: int) -> int:
+    """Copy the last F_ROW_ORDER call's row-ordered values (key-major, row
+    order within a key) into d_out (device, `capacity` floats) on the launch's
+    stream; returns their number.  Valid until the next call on that stream."""
+    lib = load()
+    err = _err()
+    n = ctypes.c_int64(-1)
+    _check(lib.wx_group_rows_last_values(ctypes.byref(launch), d_out or None, capacity, ctypes.byref(n), err,
+                                         len(err)), err)
     return n.value
 
 

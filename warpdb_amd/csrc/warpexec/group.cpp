@@ -108,7 +108,7 @@ KeyRange read_mm(Workspace &w, hipStream_t s, int64_t groups) {
 // the range of a strided 65 536-row sample (one host read)
 KeyRange sample_keys(const wx_table *t, const std::vector<UsedCol> &cols, Module *mod, Workspace &w, hipStream_t s,
                      bool timed) {
-  const unsigned grid = 64;
+  const unsigned grid = kSampleGrid;
   ensure(w, w.gp_mm, (size_t)grid * 32, false);
   WxGroupPartArgs a{};
   fill_cols(t, cols, a.col);

@@ -3,6 +3,8 @@
 // sort + fold route (wx_util.hip).
 #include "wx_host.hpp"
 
+#include <cerrno>
+
 namespace wx {
 
 // Row-order GROUP BY when the groups' keys span at most 2048 values
@@ -36,6 +38,8 @@ int64_t xf_big_groups(Module *umod, const float *svals, const int64_t *d_counts,
   }
   if (w.xf_host.empty()) return 0;
   const int n_ent = (int)(w.xf_host.size() / 4);
+  w.ro_last.big_groups = n_ent;
+  w.ro_last.big_chunks = chunks;
   ensure(w, w.xf_ent, w.xf_host.size() * 8, false);
   ensure(w, w.xf_approx, (size_t)chunks * 8, false);
   ensure(w, w.xf_rec, (size_t)chunks * 64, false);
@@ -83,7 +87,29 @@ void ro_scatter_fold(Module *gmod, Module *umod, WxRoArgs &a, int64_t passing, c
   launch(umod->fn("wx_ro_fold"), (unsigned)std::min<int64_t>(ng, 1 << 20), &f, s, timed, 64);
 }
 
+// $WARPDB_RO_RANGES=<n>: a diagnostic cap on the span path's ranges (a test
+// hook: few workgroups run many tiles each, so small tables reach the
+// scatter's cross-tile state); 0 when unset.
+int64_t ro_ranges_cap() {
+  const std::string v = env_or("WARPDB_RO_RANGES", "");
+  if (v.empty()) return 0;
+  char *end = nullptr;
+  errno = 0;
+  const long long n = std::strtoll(v.c_str(), &end, 10);
+  if (errno || end == v.c_str() || *end || n < 1)
+    fail(WX_ERR_INVALID, "WARPDB_RO_RANGES must be an integer >= 1, not '" + v + "'");
+  return n;
+}
+
 // count arguments of the span path over [kmin, kmin + span)
+// the call's record, written once its route has finished (a call that fails
+// leaves the zeroed record of do_group_sum_rows)
+void ro_done(Workspace &w, int route, const float *vals, int64_t n_values) {
+  w.ro_last.route = route;
+  w.ro_last.n_values = n_values;
+  w.ro_last_vals = vals;
+}
+
 WxRoArgs ro_args(const wx_table *t, const Spec &spec, DeviceState &d, int32_t kmin, int span, Workspace &w) {
   const int64_t n = t->n_rows;
   const int64_t tiles = (n + WX_RO_TILE_ROWS - 1) / WX_RO_TILE_ROWS;
@@ -92,7 +118,10 @@ WxRoArgs ro_args(const wx_table *t, const Spec &spec, DeviceState &d, int32_t km
   // nontemporal value stores 15.4, 16 384-row tiles at one workgroup per CU
   // 12.9 vs 12.9 (their runs halve the written bytes, 7.56 -> 5.76 GB, and
   // the time stays; profiles/r05/ro_scatter_ab.txt)
-  const int ranges = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, 2ll * d.cus));
+  int ranges = (int)std::max<int64_t>(1, std::min<int64_t>(tiles, 2ll * d.cus));
+  if (const int64_t cap = ro_ranges_cap()) ranges = (int)std::min<int64_t>(ranges, cap);
+  w.ro_last.ranges = ranges;
+  w.ro_last.tiles = tiles;
   ensure(w, w.ro_cnt, (size_t)ranges * 2048 * 4, false);
   ensure(w, w.ro_off, (size_t)ranges * 2048 * 4, false);
   ensure(w, w.ro_tot, 2 * 2048 * 4, false);
@@ -152,6 +181,7 @@ void group_rows_span(const wx_table *t, const char *val_expr, const char *key_ex
   launch(umod->fn("wx_ro_base"), 1, &b, s, timed, 1024);
   ro_scatter_fold(gmod.get(), umod.get(), a, passing, d_counts, ng, d_sums, w, s, timed);
   check_errors(w);
+  ro_done(w, WX_RO_ROUTE_ORDINARY_SPAN, static_cast<const float *>(w.ro_vals.p), passing);
 }
 
 // The span path without the ordinary call (no MIN / MAX asked): a key range
@@ -175,7 +205,10 @@ int group_rows_direct(const wx_table *t, const char *val_expr, const char *key_e
   const bool timed = (L.flags & WX_F_TIME) != 0;
   const uint64_t mkey = gp_memo_key(spec, t, spec.cols);
   auto miss = w.ro_miss.find(mkey);
-  if (miss != w.ro_miss.end() && miss->second-- > 0) return 0;  // missed lately: the ordinary call first
+  if (miss != w.ro_miss.end() && miss->second-- > 0) {  // missed lately: the ordinary call first
+    w.ro_last.why = WX_RO_WHY_RECENT_MISS;
+    return 0;
+  }
   if (miss != w.ro_miss.end()) w.ro_miss.erase(miss);
   KeyRange r;
   auto it = w.gp_memo.find(mkey);
@@ -186,8 +219,14 @@ int group_rows_direct(const wx_table *t, const char *val_expr, const char *key_e
   } else {
     r = sample_keys(t, spec.cols, gmod.get(), w, s, timed);
   }
-  if (!r.any) return 0;
-  if (r.span() > 2048) return 2;
+  if (!r.any) {
+    w.ro_last.why = WX_RO_WHY_NO_SAMPLE;
+    return 0;
+  }
+  if (r.span() > 2048) {
+    w.ro_last.why = WX_RO_WHY_WIDE;
+    return 2;
+  }
   // the sampled keys centred in the span, inside the int32 range
   int64_t lo = r.lo - (2048 - r.span()) / 2;
   lo = std::max<int64_t>(INT32_MIN, std::min<int64_t>(lo, (int64_t)INT32_MAX - 2047));
@@ -220,6 +259,7 @@ int group_rows_direct(const wx_table *t, const char *val_expr, const char *key_e
     w.gp_memo.erase(mkey);
     if (w.ro_miss.size() > 256) w.ro_miss.clear();
     w.ro_miss[mkey] = 16;
+    w.ro_last.why = WX_RO_WHY_OUTSIDE;
     return 0;
   }
   const int64_t ng = info[0];
@@ -234,6 +274,7 @@ int group_rows_direct(const wx_table *t, const char *val_expr, const char *key_e
   }
   if (ng > 0) ro_scatter_fold(gmod.get(), umod.get(), a, info[1], d_counts, ng, d_sums, w, s, timed);
   check_errors(w);
+  ro_done(w, WX_RO_ROUTE_DIRECT, ng > 0 ? static_cast<const float *>(w.ro_vals.p) : nullptr, ng > 0 ? info[1] : 0);
   return 1;
 }
 
@@ -281,6 +322,8 @@ void group_rows_general(const wx_table *t, const char *val_expr, const char *key
                         int64_t *d_counts, int64_t *d_n_groups, int64_t &ng, Workspace &w, hipStream_t s) {
   const int64_t n = t->n_rows;
   if (n > 0xffffffffll) fail(WX_ERR_UNSUPPORTED, "row-order sums sort at most 2^32 - 1 rows");
+  const bool runs = ng < 0;  // the groups from the sorted keys' runs
+  w.ro_last.ranges = w.ro_last.tiles = 0;  // (a direct attempt that missed set them)
   ensure(w, w.ro_vals, (size_t)n * 4, false);
   ensure(w, w.ro_keys, (size_t)n * 4, false);
   float *vals = static_cast<float *>(w.ro_vals.p);
@@ -344,7 +387,7 @@ void group_rows_general(const wx_table *t, const char *val_expr, const char *key
     // ascending key order -- keys, counts and first rows by run-length
     // encoding (the counts then cover the rows by construction)
     // wave ranges: at most 32 768, each a multiple of 64 rows
-    const int n_blk = (int)std::min<int64_t>(32768, std::max<int64_t>(1, (m + 16383) / 16384));
+    const int n_blk = (int)std::min<int64_t>(32768, std::max<int64_t>(1, (m + kRleWaveRows - 1) / kRleWaveRows));
     ensure(w, w.gf_chunks, 64 + (size_t)n_blk * 8, false);
     WxRleArgs r{};
     r.sk = sk;
@@ -403,6 +446,7 @@ void group_rows_general(const wx_table *t, const char *val_expr, const char *key
   // (the sorted arrays -- ro_vals / ro_keys and the sort's ping-pong
   // buffers -- stay in the workspace for the next call, as the span path's do)
   check_errors(w);
+  ro_done(w, runs ? WX_RO_ROUTE_GENERAL_RUNS : WX_RO_ROUTE_GENERAL_ORDINARY, sv, m);
 }
 
 // GROUP BY with each group's sum folded in ascending row order, one double
@@ -414,13 +458,15 @@ void group_rows_general(const wx_table *t, const char *val_expr, const char *key
 // pair sort, fold), its groups from the ordinary call or, with no MIN / MAX
 // asked, from the sorted keys' runs.  MIN / MAX always come from the
 // ordinary call (they do not depend on order).  Synchronous.
-void do_group_sum_rows(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond,
-                       const wx_launch &L, int32_t key_lo, int64_t capacity, int32_t *d_keys, double *d_sums,
-                       int64_t *d_counts, int64_t *d_n_groups, int64_t *h_n_groups, float *d_mins, float *d_maxs) {
-  Op op(L);  // recursive: the steps below take it again; the buffers stay this call's
+static void group_rows_routes(Op &op, const wx_table *t, const char *val_expr, const char *key_expr, const char *cond,
+                              const wx_launch &L, int32_t key_lo, int64_t capacity, int32_t *d_keys, double *d_sums,
+                              int64_t *d_counts, int64_t *d_n_groups, int64_t *h_n_groups, float *d_mins,
+                              float *d_maxs) {
   wx_launch L1 = L;
   L1.flags &= ~(WX_F_ROW_ORDER | WX_F_SYNC);
   const std::string rows_mode = env_or("WARPDB_GROUP_ROWS", "span");
+  (void)ro_ranges_cap();  // a bad $WARPDB_RO_RANGES fails before anything is enqueued
+  op.w.ro_last.why = WX_RO_WHY_NOT_TRIED;
   // Without MIN / MAX (they come from the ordinary call): the span path
   // straight from the table (under the same lane-order guard as below), or,
   // when the keys are known to span more than 2048 (or the general path is
@@ -430,7 +476,8 @@ void do_group_sum_rows(const wx_table *t, const char *val_expr, const char *key_
     if (blank(val_expr) || blank(key_expr)) fail(WX_ERR_INVALID, "Empty query expression");
     if (capacity < 0 || (capacity > 0 && (!d_keys || !d_sums || !d_counts)))
       fail(WX_ERR_INVALID, "group outputs must hold `capacity` entries");
-    int route = 2;
+    int route = 2;  // (WARPDB_GROUP_ROWS=general: why stays "not tried")
+    if (rows_mode == "span" && rs_rank_extra(device_state(L.device, true).arch).empty()) op.w.ro_last.why = WX_RO_WHY_NONE;
     if (rows_mode == "span")
       route = rs_rank_extra(device_state(L.device, true).arch).empty()
                   ? group_rows_direct(t, val_expr, key_expr, cond, L1, capacity, d_keys, d_sums, d_counts,
@@ -469,6 +516,26 @@ void do_group_sum_rows(const wx_table *t, const char *val_expr, const char *key_
   if (ng > 0) group_rows_general(t, val_expr, key_expr, cond, L, L1, capacity, d_keys, d_sums, d_counts, d_n_groups,
                                  ng, op.w, op.s);
   if (h_n_groups) *h_n_groups = ng;
+}
+
+void do_group_sum_rows(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond,
+                       const wx_launch &L, int32_t key_lo, int64_t capacity, int32_t *d_keys, double *d_sums,
+                       int64_t *d_counts, int64_t *d_n_groups, int64_t *h_n_groups, float *d_mins, float *d_maxs) {
+  Op op(L);  // recursive: the steps below take it again; the buffers stay this call's
+  // the call's record (wx_group_rows_last_call): all zero unless a route finishes
+  auto forget = [&op] {
+    op.w.ro_last = {0, 0, 0, 0, 0, 0, 0};
+    op.w.ro_last_vals = nullptr;
+  };
+  forget();
+  try {
+    group_rows_routes(op, t, val_expr, key_expr, cond, L, key_lo, capacity, d_keys, d_sums, d_counts, d_n_groups,
+                      h_n_groups, d_mins, d_maxs);
+  } catch (...) {
+    forget();
+    throw;
+  }
+  if (op.w.ro_last.route == WX_RO_ROUTE_NONE) forget();  // the ordinary call found no group
 }
 
 }  // namespace wx

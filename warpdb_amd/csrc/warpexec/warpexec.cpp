@@ -417,6 +417,58 @@ wx_status wx_group_part_passes(const wx_launch *launch_, int64_t *passes, char *
   });
 }
 
+wx_status wx_group_rows_geometry(wx_group_rows_geom *out, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    if (!out) fail(WX_ERR_INVALID, "null geometry output");
+    const std::string extra = env_or("WARPDB_EXTRA_DEFINES", "");
+    out->tile_rows = WX_RO_TILE_ROWS;
+    out->span_bins = kRoSpanBins;
+    out->count_span_rows = kRoCountRows;
+    out->fold_block_values = 64 * (int64_t)define_value(extra, "WX_XF_J", kXfJ);
+    out->fold_blocks_ahead = define_value(extra, "WX_XF_AHEAD", kXfAhead);
+    out->fold_small = WX_FOLD_SMALL;
+    out->starts_chunk = WX_GS_CHUNK;
+    out->rle_wave_rows = kRleWaveRows;
+    out->xf_chunk = WX_XF_CHUNK;
+    out->xf_big = WX_XF_BIG;
+    out->sample_rows = (int64_t)kSampleGrid * WX_GP_BLOCK;
+  });
+}
+
+wx_status wx_group_rows_last_call(const wx_launch *launch_, wx_group_rows_record *out, char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    if (!out) fail(WX_ERR_INVALID, "null record output");
+    const wx_launch L = launch_of(launch_);
+    *out = {0, 0, 0, 0, 0, 0, 0};
+    // (no workspace yet: nothing ran there, and none is made for the question)
+    if (Workspace *w = find_workspace(L.device, static_cast<hipStream_t>(L.stream))) {
+      OpLock lock(w->op_mu);
+      *out = w->ro_last;
+    }
+  });
+}
+
+wx_status wx_group_rows_last_values(const wx_launch *launch_, float *d_out, int64_t capacity, int64_t *n_values,
+                                    char *err, size_t errlen) {
+  return guarded(err, errlen, [&] {
+    const wx_launch L = launch_of(launch_);
+    if (n_values) *n_values = 0;
+    if (capacity < 0 || (capacity > 0 && !d_out)) fail(WX_ERR_INVALID, "the value buffer must hold `capacity` floats");
+    Workspace *w = find_workspace(L.device, static_cast<hipStream_t>(L.stream));
+    if (!w) fail(WX_ERR_INVALID, "no row-order GROUP BY ran on this (device, stream)");
+    OpLock lock(w->op_mu);
+    if (w->ro_last.route == WX_RO_ROUTE_NONE) fail(WX_ERR_INVALID, "no row-order GROUP BY ran on this (device, stream)");
+    const int64_t m = w->ro_last.n_values;
+    if (n_values) *n_values = m;
+    if (m > capacity) fail(WX_ERR_CAPACITY, "the row-ordered value array holds more than `capacity` values");
+    if (m == 0) return;
+    DevGuard guard(L.device);
+    hipStream_t s = static_cast<hipStream_t>(L.stream);
+    WX_HIP(hipMemcpyAsync(d_out, w->ro_last_vals, (size_t)m * 4, hipMemcpyDeviceToDevice, s));
+    if (L.flags & WX_F_SYNC) WX_HIP(hipStreamSynchronize(s));
+  });
+}
+
 wx_status wx_group_window_geometry(int64_t n_rows, int32_t n_sums, int32_t n_minmax, int32_t family,
                                    int32_t join_form, int32_t cus, const wx_launch *launch_, wx_group_window_geom *out,
                                    char *err, size_t errlen) {

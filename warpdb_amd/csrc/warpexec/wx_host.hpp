@@ -141,6 +141,10 @@ struct Workspace {
   // the direct span path's recent misses (a key outside the guessed span):
   // calls left before it is tried again for the same expressions / table
   std::unordered_map<uint64_t, int> ro_miss;
+  // what the last row-order GROUP BY did (wx_group_rows_last_call) and where
+  // it left its row-ordered values (wx_group_rows_last_values; null: none)
+  wx_group_rows_record ro_last = {0, 0, 0, 0, 0, 0, 0};
+  const float *ro_last_vals = nullptr;
   // row-order folds of big groups (wx_xf_big_*): entries, chunk sums, chunk records
   Buf xf_ent, xf_approx, xf_rec;
   std::vector<int64_t> xf_host;  // the entries' host copy (outlives its asynchronous upload)
@@ -488,6 +492,15 @@ const wx_u64 *sort_general_keys(Op &op, Module *own, wx_u64 *ctrs, wx_u32 *h_use
 void finish_group(Op &op, hipFunction_t finalize, void *fin_args, int64_t *ng, int64_t *h_n_groups);
 
 // group_rows.cpp
+// Sizes of the row-order kernels that only their sources name (the kernel
+// sources stay as they are: their text keys the code-object cache); the host
+// uses them and wx_group_rows_geometry reports them, and
+// tests/test_ro_layouts.py reads the sources and checks each against them.
+constexpr int kRoSpanBins = 2048;                  // WX_RO_BINS (wx_group_rows.hip)
+constexpr int kRoCountRows = WX_RO_THREADS * 8;    // one span of wx_ro_count's loop: eight rows per thread
+constexpr int kRleWaveRows = 16384;                // sorted rows per wave of wx_rle_* until 32 768 ranges are reached
+constexpr int kXfJ = 8, kXfAhead = 4;              // WX_XF_J / WX_XF_AHEAD defaults (wx_util.hip)
+constexpr int kSampleGrid = 64;                    // workgroups of wx_group_part_sample (sample_keys)
 void do_group_sum_rows(const wx_table *t, const char *val_expr, const char *key_expr, const char *cond,
                        const wx_launch &L, int32_t key_lo, int64_t capacity, int32_t *d_keys, double *d_sums,
                        int64_t *d_counts, int64_t *d_n_groups, int64_t *h_n_groups, float *d_mins, float *d_maxs);
